@@ -27,10 +27,20 @@ cache of a frozen backbone stays valid for the whole run.  ``steady_ms_per_step`
 timed window alone.  ``vs_baseline`` divides by the reference's best measured throughput,
 1.87 impressions/s (CPU fp32, bs 16): a like-for-like speedup it is not.
 
-After the timed window (``--round``, default on for the cached configs) one full FedAvg
-round is timed end to end: a whole local epoch of GA steps over the client's shard, the
-validation pass over its whole validation split, and the closing metrics all-reduce;
-``round_s`` / ``round_impressions_per_s`` report it and ``valid_auc`` comes from it.
+A plain run does only what the headline needs: set-up, cache build, warm-up, the timed
+steps, the result line.  ``--dump-outputs DIR`` also writes what the last timed step left
+with its caller as ``DIR/<name>.npy`` (float32): ``loss`` (that step's loss), ``losses``
+(every timed step's) and ``params`` (the flat trainable parameters after its optimizer
+update; a fixed seeded sample where they exceed the size budget).  The inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
+
+``--full`` adds everything else, after the timed window and the dump.  One full FedAvg round
+(``--round``, default on for the cached configs) is timed end to end: a whole local epoch of
+GA steps over the client's shard, the validation pass over its whole validation split, and
+the closing metrics all-reduce; ``round_s`` / ``round_impressions_per_s`` report it and
+``valid_auc`` comes from it.  Then the learning probe (``--no-probe`` skips it), and at N > 1
+the gradient bucket's all-reduce alone, RCCL against the custom IPC all-reduce.  Without
+``--full`` those fields of the result line are null.
 
 Single GPU: ``python bench.py``; N GPUs: ``torchrun --nproc-per-node N bench.py --gpus N``.
 """
@@ -58,11 +68,33 @@ MODES = {2: "Gradient_Averaging (all-reduce of the flat 4.66 MB grad bucket per 
             "in 28 MB buckets during the backward)"}
 
 
+DUMP_BUDGET_BYTES = 60 << 20  # all files of one --dump-outputs together
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """``path/<name>.npy`` in float32.  An array over its share of the budget is cut to a fixed
+    sample: sorted indices drawn with seed 0, the same for every run of the same shape."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // 4 // len(arrays)  # elements per array
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.size > cap:
+            a = a.ravel()[np.sort(np.random.default_rng(0).integers(0, a.size, size=cap))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: the FedAvg round "
+                         "(--round), validation, the learning probe, the all-reduce comparison at N > 1")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs (loss, losses, params) as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=64, help="impressions per GPU per step")
     ap.add_argument("--preset", default="mind-small")
     ap.add_argument("--config", type=int, default=2, choices=[2, 3, 4, 5],
@@ -75,13 +107,14 @@ def main() -> int:
     ap.add_argument("--cache-warm", type=int, default=512,
                     help="titles run through the backbone (result dropped) before the timed cache build")
     ap.add_argument("--profile-phases", action="store_true")
-    ap.add_argument("--no-probe", action="store_true", help="skip the untimed learning probe after the round")
+    ap.add_argument("--no-probe", action="store_true",
+                    help="with --full: skip the untimed learning probe after the round")
     ap.add_argument("--step-events", action="store_true",
                     help="diagnostic: a timing event after every timed step's launch (device interval per step)")
     ap.add_argument("--news-cache", default="auto", choices=["auto", "hidden", "none"],
                     help="HBM hidden-state cache of the frozen backbone (none = re-encode every step)")
     ap.add_argument("--round", default="auto", choices=["auto", "on", "off"],
-                    help="time one full FedAvg round (local epoch + validation) after the timed steps")
+                    help="with --full: time one full FedAvg round (local epoch + validation) after the timed steps")
     ap.add_argument("--backbone", default="", help="test-only override of the backbone preset (e.g. 'tiny' for the "
                                                     "multi-process CPU test); the reported model says so")
     args = ap.parse_args()
@@ -260,6 +293,10 @@ def main() -> int:
             dist.all_reduce(tu, group=ctx.ctrl_group)
             u_mean = float(tu.item()) / world
     loss = float(torch.stack(losses).float().mean())
+    if args.dump_outputs and ctx.rank == 0:  # before anything below trains the model further
+        lv = torch.stack([x.detach().reshape(()) for x in losses]).float().cpu().numpy()
+        dump_outputs(args.dump_outputs, {"loss": lv[-1:], "losses": lv,
+                                         "params": model.flat.flat.detach().float().cpu().numpy().ravel()})
     if ctx.initialized:  # FEDREC_COLL_CHECK=1: every client issued the same collective sequence
         from fedrec_with_pytorchdistributed_amd.parallel.collcheck import CHECK
         CHECK.verify(ctx.ctrl_group, "bench")
@@ -268,7 +305,7 @@ def main() -> int:
     # vs the custom IPC all-reduce (bus bandwidth = 2 (W-1)/W x bytes / time): configs 2-4 the
     # flat fp32 4.66 MB bucket, config 5 one 28 MB int32 (masked) bucket of the reducer
     comm_ms = busbw = ipc_info = None
-    if ctx.initialized and world > 1 and dev.type == "cuda":
+    if args.full and ctx.initialized and world > 1 and dev.type == "cuda":
         if args.config == 5:
             g = torch.zeros(7 << 20, dtype=torch.int32, device=dev)
         else:
@@ -322,7 +359,7 @@ def main() -> int:
     # one full FedAvg round, end to end: a whole local epoch of synchronous steps (every
     # client runs the same number of steps, so the collectives match), validation over the
     # whole validation split, the closing metrics all-reduce
-    do_round = args.round == "on" or (args.round == "auto" and eng.hcache is not None)
+    do_round = args.full and (args.round == "on" or (args.round == "auto" and eng.hcache is not None))
     rnd = None
     auc = None
     if do_round:
@@ -352,7 +389,7 @@ def main() -> int:
                "round_train_loss": round(st["training_loss"], 5), "round_valid_impressions": int(mv["n_valid"])}
         if cache_s is not None:  # a first round also pays for the cache build
             rnd["first_round_s"] = round(round_s + cache_s, 4)
-    elif not args.no_valid:
+    elif args.full and not args.no_valid:
         auc = reduce_valid(eng.validate(batch_size=256, limit=args.valid_limit))
 
     # learning probe (after everything above, untimed): the reference's sigmoid-CE scorer keeps
@@ -392,6 +429,7 @@ def main() -> int:
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(1000.0 * charged / args.steps, 3),
             "higher_is_better": True,
             "scaling": "weak",

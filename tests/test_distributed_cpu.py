@@ -382,7 +382,7 @@ def test_bench_contract_two_ranks(config):
     """bench.py under the driver's multi-rank launch contract (gloo here, RCCL on the node):
     exactly one JSON line, from rank 0, with the whole-job value and the BASELINE metric."""
     argv = ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--preset", "tiny",
-            "--backbone", "tiny", "--config", str(config), "--pa-every", "1", "--valid-limit", "16"]
+            "--backbone", "tiny", "--config", str(config), "--pa-every", "1", "--valid-limit", "16", "--full"]
     outs = run_ranks([argv, argv], timeout=300)
     _ok(outs)
     lines = [[l for l in out.splitlines() if l.startswith("{")] for _, out in outs]

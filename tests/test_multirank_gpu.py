@@ -34,7 +34,8 @@ def test_grad_avg_two_clients_on_gpu_stay_identical(tmp_path, dev):
 
 @pytest.mark.gpu
 def test_bench_two_clients_on_gpu(dev):
-    argv = ["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "2", "--preset", "small", "--valid-limit", "64"]
+    argv = ["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "2", "--preset", "small", "--valid-limit", "64",
+            "--full"]
     outs = run_ranks([argv, argv], SHARE, timeout=400)
     _ok(outs)
     lines = [[l for l in out.splitlines() if l.startswith("{")] for _, out in outs]
@@ -74,7 +75,7 @@ def test_bench_configs_multi_client_on_gpu(dev, config, ranks):
     plane): GA at 4 ranks, parameter averaging, LDP, and the unfrozen BERT-base with secure
     aggregation (pairwise masks over the store, int32 all-reduce)."""
     argv = ["bench.py", "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--preset", "small", "--valid-limit", "32",
-            "--config", str(config), "--pa-every", "1"]
+            "--config", str(config), "--pa-every", "1", "--full"]
     if config == 5:
         argv += ["--batch", "16"]
     outs = run_ranks([argv] * ranks, SHARE, timeout=600)

@@ -18,7 +18,8 @@ from fedrec_with_pytorchdistributed_amd.eval import metrics as M
 from fedrec_with_pytorchdistributed_amd.models.fedrec_model import FedRecModel
 from fedrec_with_pytorchdistributed_amd.ops import reference as ref
 
-REF_DATA = "/root/reference/UserData"
+# the reference's shipped sample shard (its programs' input data), stored with the tests
+REF_DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "UserData")
 
 
 # ---------------------------------------------------------------------------------------
@@ -39,7 +40,6 @@ def test_safe_pickle_roundtrip_and_refusal(tmp_path):
         safe_pickle.loads(pickle.dumps(collections.OrderedDict(a=1)))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="reference shard not mounted")
 def test_reference_shard_loads_safely():
     s = Shard.load(REF_DATA)  # E1: [225,2,50] int64, 139 nids, 4 train + 1 valid rows of user U10256
     assert s.news_index.shape == (225, 2, 50) and s.news_index.dtype == np.int64
