@@ -160,6 +160,10 @@ int fr_title_attention_bwd_drop_bf16(const void* qkv, const void* dout, const in
 int fr_gather_dropout(const float* v, const int* idx, void* out, int out_bf16, int M, int K, float p,
                       unsigned long long seed, unsigned long long offset, const unsigned long long* dev_off,
                       hipStream_t s);
+void fr_topk_set_splits(int s);
+int fr_topk_splits(long B, long N);
+int fr_topk_scores(const float* user, const float* table, const int* exclude, void* ws, float* scores, int* ids, long B,
+                   long N, int D, long E, int k, int min_id, hipStream_t s);
 long fr_wgrad_bf16(const void* dY, const void* X, float* C, float* scratch, int M, int N, int K, int accumulate,
                    hipStream_t s);
 }
@@ -1937,6 +1941,46 @@ at::Tensor wgrad(const at::Tensor& dy, const at::Tensor& x) {
   return C;
 }
 
+// ---- catalog top-k (topk_scores.hip): scores = user table^T fused with an ordered top-k select ----
+// -> (scores [B, k] fp32, ids [B, k] int32): the k best rows n >= min_id, n not in exclude[b, :],
+// score not NaN, by (score descending, id ascending); short lists end in (-inf, -1)
+std::tuple<at::Tensor, at::Tensor> topk_scores(const at::Tensor& user, const at::Tensor& table, int64_t k,
+                                               const c10::optional<at::Tensor>& exclude, int64_t min_id) {
+  check_dev(user, "user");
+  check_dev(table, "table");
+  TORCH_CHECK(user.scalar_type() == at::kFloat && table.scalar_type() == at::kFloat,
+              "fedrec::topk_scores: user / table must be fp32 (got ", user.scalar_type(), " / ", table.scalar_type(), ")");
+  TORCH_CHECK(user.dim() == 2 && table.dim() == 2 && user.size(1) == table.size(1),
+              "fedrec::topk_scores: user [B, D], table [N, D]");
+  TORCH_CHECK(user.device() == table.device(), "fedrec::topk_scores: user and table on one device");
+  const int64_t B = user.size(0), N = table.size(0), D = user.size(1);
+  TORCH_CHECK(k >= 1 && k <= 128, "fedrec::topk_scores: 1 <= k <= 128 (got ", k, ")");
+  TORCH_CHECK(D % 4 == 0 && D >= 4 && D <= 512, "fedrec::topk_scores: D % 4 == 0, 4 <= D <= 512 (got ", D, ")");
+  TORCH_CHECK(B >= 1 && N >= 1 && N < 2147483648LL, "fedrec::topk_scores: B >= 1, 1 <= N < 2^31");
+  int64_t E = 0;
+  const int* ep = nullptr;
+  if (exclude.has_value() && exclude->defined()) {
+    check_dev(*exclude, "exclude");
+    TORCH_CHECK(exclude->scalar_type() == at::kInt && exclude->dim() == 2 && exclude->size(0) == B &&
+                    exclude->device() == user.device(),
+                "fedrec::topk_scores: exclude int32 [B, E] on the user's device");
+    E = exclude->size(1);
+    if (E > 0) ep = exclude->data_ptr<int>();
+  }
+  const int mid = (int)std::min<int64_t>(std::max<int64_t>(min_id, 0), 2147483647LL);
+  const c10::DeviceGuard g(user.device());
+  auto scores = at::empty({B, k}, user.options());
+  auto ids = at::empty({B, k}, user.options().dtype(at::kInt));
+  auto ws = at::empty({B, (int64_t)fr_topk_splits((long)B, (long)N), k}, user.options().dtype(at::kLong));
+  const int rc = fr_topk_scores(user.data_ptr<float>(), table.data_ptr<float>(), ep, ws.data_ptr(),
+                                scores.data_ptr<float>(), ids.data_ptr<int>(), (long)B, (long)N, (int)D, (long)E, (int)k,
+                                mid, cur_stream());
+  TORCH_CHECK(rc != 2, "fedrec::topk_scores: user / table must be 16-byte aligned");
+  check_rc(rc, "topk_scores");
+  return {scores, ids};
+}
+void topk_set_splits(int64_t s) { fr_topk_set_splits((int)s); }
+
 void gemm_set_variant(int64_t v) { fr_gemm_set_variant((int)v); }
 void title_attn_set_waves(int64_t w) { fr_title_attn_set_waves((int)w); }
 void title_attn_bwd_set_variant(int64_t v) { fr_title_attn_bwd_set_variant((int)v); }
@@ -1962,6 +2006,8 @@ TORCH_LIBRARY(fedrec, m) {
   m.def("head_score_set_rows(int r) -> ()", &head_score_set_rows);
   m.def("head_score_set_ilv(int v) -> ()", &head_score_set_ilv);
   m.def("ln_set_wide(int v) -> ()", &ln_set_wide);
+  m.def("topk_set_splits(int s) -> ()", &topk_set_splits);
+  m.def("topk_scores(Tensor user, Tensor table, int k, Tensor? exclude=None, int min_id=0) -> (Tensor, Tensor)");
   m.def("linear(Tensor x, Tensor w, Tensor? b, int act, Tensor? residual) -> Tensor");
   m.def("linear_gelu_bwd(Tensor x, Tensor w, Tensor z) -> (Tensor, Tensor)");
   m.def("gelu_bwd_colsum(Tensor df, Tensor z) -> (Tensor, Tensor)");
@@ -2094,4 +2140,5 @@ TORCH_LIBRARY_IMPL(fedrec, CUDA, m) {
   m.impl("title_attention_bwd_drop", &title_attention_bwd_drop);
   m.impl("wgrad", &wgrad);
   m.impl("gather_dropout", &gather_dropout);
+  m.impl("topk_scores", &topk_scores);
 }

@@ -118,3 +118,20 @@ def metric_sums(scores: np.ndarray) -> np.ndarray:
     if n == 0:
         return np.zeros(5)
     return np.array([m["auc"] * n, m["mrr"] * n, m["ndcg5"] * n, m["ndcg10"] * n, n], dtype=np.float64)
+
+
+def topk_metrics(ids: np.ndarray, pos: np.ndarray) -> Dict[str, float]:
+    """Full-catalog ranking quality of ordered top-k lists ``ids [I, k]`` (-1 = empty slot) against
+    one held-out positive ``pos [I]`` per impression: ``hr@k`` (the positive is in the list),
+    ``ndcg@k`` (``1 / log2(rank + 1)`` if it is ranked within k, else 0 -- the ideal DCG of a
+    single positive is 1), ``mrr@k`` (``1 / rank`` or 0), corpus means, and ``n``."""
+    ids = np.asarray(ids)
+    pos = np.asarray(pos).reshape(-1)
+    k = int(ids.shape[1]) if ids.ndim == 2 else 0
+    if ids.ndim != 2 or ids.shape[0] == 0:
+        return {f"hr@{k}": float("nan"), f"ndcg@{k}": float("nan"), f"mrr@{k}": float("nan"), "k": k, "n": 0}
+    hit = ids == pos[:, None]
+    found = hit.any(1)
+    rank = np.where(found, hit.argmax(1) + 1, 1).astype(np.float64)
+    return {f"hr@{k}": float(found.mean()), f"ndcg@{k}": float(np.where(found, 1.0 / np.log2(rank + 1.0), 0.0).mean()),
+            f"mrr@{k}": float(np.where(found, 1.0 / rank, 0.0).mean()), "k": k, "n": int(ids.shape[0])}

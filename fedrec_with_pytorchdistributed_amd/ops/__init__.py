@@ -23,6 +23,8 @@ segment_sum_rows      client.py:26-48,87-89        news_grad.hip: deterministic 
                       (K16, K17)                   + LDP clip + Philox Gaussian noise
 adam_flat             model.py:89,93 (K20)         adam.hip: one pass over the flat buffer
 dedup / sample_batch  dataset.py:69-86 (K18)       batch.hip: on-device sampling + unique
+topk_scores           (beyond the reference)       topk_scores.hip: fp32 MFMA U V^T fused with an
+                                                   ordered per-user top-k (no [B, N] matrix)
 ====================  ===========================  ===========================================
 """
 from __future__ import annotations
@@ -220,6 +222,19 @@ def score_ce_rows(table, ci, user, act: str, dcand_out):
                                                    act)
     dcand_out.copy_(dcand.reshape(dcand_out.shape))
     return loss, scores, du
+
+
+def topk_scores(user, table, k: int, exclude=None, min_id: int = 0):
+    """Catalog top-k -> ``(scores [B, k] fp32, ids [B, k] int32)``: the ``k`` best rows of ``table
+    [N, D]`` for each row of ``user [B, D]`` by raw dot product (fp32 operands and accumulation),
+    ordered by (score descending, id ascending).  Row ``n`` is eligible iff ``n >= min_id``, ``n`` is
+    not in ``exclude[b, :]`` (int [B, E]; entries < 0 or >= N and duplicates are ignored) and its
+    score is not NaN; slots past the eligible count hold ``(-inf, -1)``.  The device kernel never
+    writes the ``[B, N]`` scores and is bitwise independent of its grid (csrc/topk_scores.hip)."""
+    if _dev(user):
+        ex = None if exclude is None else exclude.to(torch.int32).contiguous()
+        return tuple(native.require_for(user).topk_scores(user, table, int(k), ex, int(min_id)))
+    return ref.topk_scores(user, table, int(k), exclude, int(min_id))
 
 
 def segment_sum_rows(rows, inv, num_out: int, clip: float = 0.0, noise_std: float = 0.0,

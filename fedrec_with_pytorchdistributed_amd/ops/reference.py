@@ -326,3 +326,41 @@ def title_plan(mask: torch.Tensor):
     i32 = torch.int32
     return (rowmap.to(i32), src.to(i32), kv_start.to(i32), kv_len.to(i32), qstart.to(i32),
             torch.tensor([R], dtype=i32))
+
+
+# ---------------------------------------------------------------------------------------
+# Catalog top-k (oracle of csrc/topk_scores.hip)
+# ---------------------------------------------------------------------------------------
+def topk_scores(user: torch.Tensor, table: torch.Tensor, k: int, exclude: Optional[torch.Tensor] = None,
+                min_id: int = 0, chunk: int = 256):
+    """``s[b, n] = user[b] . table[n]`` in the dtype given -> ``(scores [B, k], ids [B, k] int32)``:
+    the ``k`` best rows of each user by (score descending, id ascending) among the eligible rows
+    -- ``n >= min_id``, ``n`` not in ``exclude[b, :]`` (entries < 0 or >= N and duplicates are
+    ignored), ``s[b, n]`` not NaN.  Slots past the eligible count hold ``(-inf, -1)``.  Users run
+    in chunks, so at most a ``[chunk, N]`` block of scores exists at a time.  The order comes from
+    two stable sorts (score descending over the ascending ids, then eligible rows first), never
+    from ``torch.topk``'s tie order."""
+    B, N = user.shape[0], table.shape[0]
+    k = int(k)
+    scores = torch.full((B, k), float("-inf"), dtype=user.dtype)
+    ids = torch.full((B, k), -1, dtype=torch.int32)
+    kk = min(k, N)
+    row_ok = torch.arange(N) >= int(min_id)
+    for s in range(0, B, chunk):
+        sc = user[s:s + chunk] @ table.t()
+        c = sc.shape[0]
+        elig = row_ok[None, :] & ~torch.isnan(sc)
+        if exclude is not None and exclude.shape[1] > 0:
+            ex = exclude[s:s + chunk].long()
+            hit = torch.zeros(c, N + 1, dtype=torch.bool)
+            hit.scatter_(1, torch.where((ex >= 0) & (ex < N), ex, torch.full_like(ex, N)), True)
+            elig &= ~hit[:, :N]
+        key = torch.where(elig, sc, torch.full_like(sc, float("-inf")))
+        order = torch.sort(key, dim=1, descending=True, stable=True).indices
+        # eligible rows first (an eligible score may itself be -inf); stable: keeps the order above
+        front = torch.sort((~elig).gather(1, order).to(torch.int8), dim=1, stable=True).indices
+        top = order.gather(1, front)[:, :kk]
+        ok = elig.gather(1, top)
+        scores[s:s + c, :kk] = torch.where(ok, sc.gather(1, top), torch.full_like(sc[:, :kk], float("-inf")))
+        ids[s:s + c, :kk] = torch.where(ok, top, torch.full_like(top, -1)).to(torch.int32)
+    return scores, ids

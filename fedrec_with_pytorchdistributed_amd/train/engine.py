@@ -41,7 +41,7 @@ from .. import ops
 from ..config import FedRecConfig
 from ..data.sampler import DeviceSampler, HostSampler, validation_batches
 from ..data.shard import Shard
-from ..eval.metrics import batch_metrics
+from ..eval.metrics import batch_metrics, topk_metrics
 from ..models.fedrec_model import FedRecModel
 from ..ops import functional as OF
 from ..ops import native
@@ -1083,3 +1083,76 @@ class LocalEngine:
             out.update({"valid_auc": round(m["last_auc"], 2), "valid_mrr": round(m["last_mrr"], 2),
                         "val_ndcg@5": round(m["last_ndcg5"], 2), "val_ndcg@10": round(m["last_ndcg10"], 2)})
         return out
+
+    # ---- catalog recommendation (beyond the reference: it stops at the sampled-candidate AUC) ----
+    def _catalog_table(self, table: Optional[torch.Tensor]) -> torch.Tensor:
+        if table is not None:
+            return table
+        return self.news_table if self.news_table is not None else self.encode_all(grad=False)
+
+    @torch.no_grad()
+    def user_vectors(self, his, table: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """User vectors ``[B, 400]`` fp32 of histories ``his [B, H]`` (news ids, 0 = padding): eval
+        mode (no dropout), padded slots masked when ``mask_padding`` is on.  The history rows are
+        gathered from ``table`` (default: the epoch's news table, else a fresh :meth:`encode_all`)."""
+        self.sync_params()
+        table = self._catalog_table(table)
+        self.model.eval()
+        his = self.to_device(his).to(torch.int32)
+        B, H = his.shape
+        his_v = table.index_select(0, his.reshape(-1).long()).view(B, H, -1)
+        return self.model.user_encoder(his_v, his).float().contiguous()
+
+    @torch.no_grad()
+    def recommend(self, his, k: int = 10, exclude_history: bool = True,
+                  table: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The ``k`` best news of the whole catalog for each history -> ``(ids [B, k] int32, scores
+        [B, k] fp32)``, best first (ties by ascending id; ``-1`` / ``-inf`` past the eligible count).
+        The ``<unk>`` row 0 is never returned, nor -- with ``exclude_history`` -- anything the user
+        clicked.  Scores are the raw dot products ``u . v`` (the model's sigmoid is monotone, so the
+        ranking is the model's).  One :meth:`encode_all` per call unless ``table`` is passed."""
+        table = self._catalog_table(table)
+        his = self.to_device(his).to(torch.int32).contiguous()
+        u = self.user_vectors(his, table)
+        scores, ids = ops.topk_scores(u, table.float().contiguous(), int(k), his if exclude_history else None, 1)
+        return ids, scores
+
+    @torch.no_grad()
+    def recommend_valid(self, k: int = 10, batch_size: int = 256, limit: Optional[int] = None,
+                        return_lists: bool = False):
+        """Full-catalog ranking quality over the validation impressions: each impression's history
+        (truncated as in :meth:`validate`) ranks the catalog minus the history -- the held-out
+        positive is not excluded -- and ``hr@k`` / ``ndcg@k`` / ``mrr@k`` of the positive come from
+        :func:`eval.metrics.topk_metrics`.  The news table is built once, the per-batch lists stay
+        in device buffers and ONE copy brings them back.  ``return_lists``: ``(metrics, ids, scores)``
+        with the ``[n, k]`` host arrays."""
+        self.sync_params()
+        arr = self.shard.valid
+        n = len(arr) if limit is None else min(int(limit), len(arr))
+        k = int(k)
+        if n == 0:
+            m = topk_metrics(np.zeros((0, k), np.int32), np.zeros(0, np.int32))
+            return (m, np.zeros((0, k), np.int32), np.zeros((0, k), np.float32)) if return_lists else m
+        table = self._catalog_table(None).float().contiguous()
+        truncate = not self.q.no_history_truncation
+        if self.device.type == "cuda" and self.fused_user and truncate:
+            self.prepare_validation(batch_size)
+            batches = (h for _, h in self._vsampler.valid_batches(batch_size, n))
+        else:
+            batches = (h for _, h in validation_batches(arr, batch_size, self.cfg.npratio, self.cfg.max_his_len,
+                                                        truncate, n))
+        IDS = torch.empty(n, k, dtype=torch.int32, device=self.device)
+        SC = torch.empty(n, k, dtype=torch.float32, device=self.device)
+        s0 = 0
+        for his in batches:
+            ids, sc = self.recommend(his, k, True, table)
+            B = ids.shape[0]
+            IDS[s0:s0 + B].copy_(ids)
+            SC[s0:s0 + B].copy_(sc)
+            s0 += B
+        # the one copy back (int32 ids ride along as raw bits of the fp32 buffer)
+        host = torch.cat([IDS.view(torch.float32).reshape(-1), SC.reshape(-1)]).cpu().numpy()
+        ids_h = host[:n * k].view(np.int32).reshape(n, k)
+        sc_h = host[n * k:].reshape(n, k)
+        m = topk_metrics(ids_h, np.asarray(arr.pos[:n]))
+        return (m, ids_h, sc_h) if return_lists else m
