@@ -5,6 +5,11 @@
 //   m = b1 m + (1-b1) g' ;  v = b2 v + (1-b2) g'^2
 //   p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)          (torch.optim.Adam, no weight decay)
 //
+// The weights 1-b1 / 1-b2 come from the host, formed in double from the double betas and
+// rounded once (omb1 / omb2), as torch.optim.Adam's `1 - beta`: 1.f - (float)0.999 is
+// 0.00099998713, a 1.3e-5 relative error in v on every step.  Both kernels below take them
+// the same way, and both bias corrections are 1 - pow(double beta, t) in double.
+//
 // One streaming pass, float4 vectorised; optionally writes a bf16 copy of p (unfrozen
 // backbone: the compute weights are refreshed in the same pass).
 #include "common.h"
@@ -13,8 +18,9 @@ namespace {
 
 __global__ __launch_bounds__(256) void adam_kernel(float4* __restrict__ p, const float4* __restrict__ g,
                                                    float4* __restrict__ m, float4* __restrict__ v,
-                                                   bf16x4* __restrict__ plow, long n4, float lr, float b1, float b2,
-                                                   float eps, float step_size, float inv_sqrt_bc2, float gs) {
+                                                   bf16x4* __restrict__ plow, long n4, float b1, float b2, float omb1,
+                                                   float omb2, float eps, float step_size, float inv_sqrt_bc2,
+                                                   float gs) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     float4 pp = p[i], gg = g[i], mm = m[i], vv = v[i];
     float* pa = (float*)&pp;
@@ -24,8 +30,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float4* __restrict__ p, const
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float x = ga[k] * gs;
-      ma[k] = b1 * ma[k] + (1.f - b1) * x;
-      va[k] = b2 * va[k] + (1.f - b2) * x * x;
+      ma[k] = b1 * ma[k] + omb1 * x;
+      va[k] = b2 * va[k] + omb2 * x * x;
       const float denom = sqrtf(va[k]) * inv_sqrt_bc2 + eps;
       pa[k] -= step_size * ma[k] / denom;
     }
@@ -39,14 +45,15 @@ __global__ __launch_bounds__(256) void adam_kernel(float4* __restrict__ p, const
 }  // namespace
 
 extern "C" int fr_adam_flat(float* p, const float* g, float* m, float* v, void* plow, long n, float lr, float b1,
-                            float b2, float eps, float bc1, float bc2, float grad_scale, hipStream_t s) {
+                            float b2, float omb1, float omb2, float eps, float bc1, float bc2, float grad_scale,
+                            hipStream_t s) {
   if (n % 4 != 0) return 1;
   const long n4 = n / 4;
   if (n4 == 0) return 0;
   long blocks = (n4 + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (float4*)p, (const float4*)g, (float4*)m,
-                     (float4*)v, (bf16x4*)plow, n4, lr, b1, b2, eps, lr / bc1, 1.0f / sqrtf(bc2), grad_scale);
+                     (float4*)v, (bf16x4*)plow, n4, b1, b2, omb1, omb2, eps, lr / bc1, 1.0f / sqrtf(bc2), grad_scale);
   return 0;
 }
 
@@ -55,7 +62,8 @@ extern "C" int fr_adam_flat(float* p, const float* g, float* m, float* v, void* 
 // training step (forward, backward, Adam) when no gradient all-reduce sits between the
 // backward and the optimizer (one client): every block reads t (the step's cast launch -- the
 // graph's first kernel -- advanced the counter) and forms the bias corrections itself (in
-// double, then rounded as the host path rounds them); block 0 also copies this step's loss
+// double from the double betas, then rounded to fp32: the host path's values up to the last
+// bit of a double pow); block 0 also copies this step's loss
 // into slot (t - 1) % ring of a loss ring (no per-step clone launch).
 namespace {
 // Gradient segments (optional): the fresh per-parameter gradient tensors where autograd left
@@ -100,8 +108,9 @@ __device__ __forceinline__ float4 seg_grad4(const SegLds& sg, int nseg, long e) 
 
 __global__ __launch_bounds__(256) void adam_dev_kernel(float4* __restrict__ p, float4* __restrict__ g,
                                                        float4* __restrict__ m, float4* __restrict__ v,
-                                                       bf16x4* __restrict__ plow, long n4, float lr, float b1, float b2,
-                                                       float eps, float gs, const long long* __restrict__ step,
+                                                       bf16x4* __restrict__ plow, long n4, float lr, double b1d,
+                                                       double b2d, float omb1, float omb2, float eps, float gs,
+                                                       const long long* __restrict__ step,
                                                        const float* __restrict__ loss, float* __restrict__ ring,
                                                        int ring_n, const AdamSegs segs,
                                                        const int* __restrict__ skip) {
@@ -123,9 +132,10 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float4* __restrict__ p, f
     sg_s.n[threadIdx.x] = segs.n[threadIdx.x];
   }
   const long long t = step[0];
-  if (threadIdx.x == 0) {  // double pow once per block, as the host computes them for the eager kernel
-    bc_s[0] = (float)(1.0 - pow((double)b1, (double)t));
-    bc_s[1] = (float)(1.0 - pow((double)b2, (double)t));
+  const float b1 = (float)b1d, b2 = (float)b2d;
+  if (threadIdx.x == 0) {  // double pow of the double betas once per block, as the host's for the eager kernel
+    bc_s[0] = (float)(1.0 - pow(b1d, (double)t));
+    bc_s[1] = (float)(1.0 - pow(b2d, (double)t));
   }
   __syncthreads();
   const float bc1 = bc_s[0], bc2 = bc_s[1];
@@ -146,8 +156,8 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float4* __restrict__ p, f
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float x = ga[k] * gs;
-      ma[k] = b1 * ma[k] + (1.f - b1) * x;
-      va[k] = b2 * va[k] + (1.f - b2) * x * x;
+      ma[k] = b1 * ma[k] + omb1 * x;
+      va[k] = b2 * va[k] + omb2 * x * x;
       const float denom = sqrtf(va[k]) * inv_sqrt_bc2 + eps;
       pa[k] -= step_size * ma[k] / denom;
     }
@@ -163,10 +173,10 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float4* __restrict__ p, f
 
 // nseg > 0: the gradient is gathered from the segments (gsrc / goff / gn, sorted by offset;
 // a null source = no gradient) and written into g
-extern "C" int fr_adam_dev(float* p, float* g, float* m, float* v, void* plow, long n, float lr, float b1,
-                           float b2, float eps, float grad_scale, const long long* step, const float* loss, float* ring,
-                           int ring_n, hipStream_t s, int nseg, const float* const* gsrc, const long* goff,
-                           const long* gn, const int* skip) {
+extern "C" int fr_adam_dev(float* p, float* g, float* m, float* v, void* plow, long n, float lr, double b1,
+                           double b2, float omb1, float omb2, float eps, float grad_scale, const long long* step,
+                           const float* loss, float* ring, int ring_n, hipStream_t s, int nseg,
+                           const float* const* gsrc, const long* goff, const long* gn, const int* skip) {
   if (n % 4 != 0 || (ring != nullptr && (loss == nullptr || ring_n < 1))) return 1;
   if (nseg < 0 || nseg > ADAM_SEG) return 2;
   AdamSegs segs{};
@@ -182,7 +192,8 @@ extern "C" int fr_adam_dev(float* p, float* g, float* m, float* v, void* plow, l
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(adam_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (float4*)p, (float4*)g, (float4*)m,
-                     (float4*)v, (bf16x4*)plow, n4, lr, b1, b2, eps, grad_scale, step, loss, ring, ring_n, segs, skip);
+                     (float4*)v, (bf16x4*)plow, n4, lr, b1, b2, omb1, omb2, eps, grad_scale, step, loss, ring, ring_n,
+                     segs, skip);
   return 0;
 }
 // ---------------------------------------------------------------------------------------

@@ -95,11 +95,12 @@ int fr_segment_sum_rows_ldp(const float* rows, const int* perm, const int* seg_p
                             unsigned long long offset, const unsigned long long* dev_off, hipStream_t s);
 int fr_ldp_rows(const float* rows, float* out, int R, int D, float clip, float noise_std, unsigned long long seed,
                 unsigned long long offset, hipStream_t s, const unsigned long long* dev_off);
-int fr_adam_dev(float* p, float* g, float* m, float* v, void* plow, long n, float lr, float b1, float b2, float eps,
-                float grad_scale, const long long* step, const float* loss, float* ring, int ring_n, hipStream_t s,
-                int nseg, const float* const* gsrc, const long* goff, const long* gn, const int* skip);
+int fr_adam_dev(float* p, float* g, float* m, float* v, void* plow, long n, float lr, double b1, double b2, float omb1,
+                float omb2, float eps, float grad_scale, const long long* step, const float* loss, float* ring,
+                int ring_n, hipStream_t s, int nseg, const float* const* gsrc, const long* goff, const long* gn,
+                const int* skip);
 int fr_adam_flat(float* p, const float* g, float* m, float* v, void* plow, long n, float lr, float b1, float b2,
-                 float eps, float bc1, float bc2, float grad_scale, hipStream_t s);
+                 float omb1, float omb2, float eps, float bc1, float bc2, float grad_scale, hipStream_t s);
 int fr_sample_batch(const int* rows, const int* pos, const long long* neg_ptr, const int* negs, const long long* his_ptr,
                     const int* his, int* cand, int* hout, int B, int npr, int H, int truncate, unsigned long long seed,
                     unsigned long long offset, int valid, hipStream_t s);
@@ -1146,10 +1147,10 @@ void adam_dev(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, const at::
     }
   }
   check_rc(fr_adam_dev(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), nullptr,
-                       (long)p.numel(), (float)lr, (float)b1, (float)b2, (float)eps, (float)grad_scale,
-                       (const long long*)step.data_ptr<int64_t>(), has_ring ? loss.data_ptr<float>() : nullptr,
-                       has_ring ? ring.data_ptr<float>() : nullptr, (int)ring.numel(), cur_stream(), (int)sp.size(),
-                       sp.data(), so.data(), sn.data(), skp),
+                       (long)p.numel(), (float)lr, b1, b2, (float)(1.0 - b1), (float)(1.0 - b2), (float)eps,
+                       (float)grad_scale, (const long long*)step.data_ptr<int64_t>(),
+                       has_ring ? loss.data_ptr<float>() : nullptr, has_ring ? ring.data_ptr<float>() : nullptr,
+                       (int)ring.numel(), cur_stream(), (int)sp.size(), sp.data(), so.data(), sn.data(), skp),
            "adam_dev");
 }
 
@@ -1169,8 +1170,8 @@ void adam_flat(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v, co
   }
   const c10::DeviceGuard dg(p.device());
   check_rc(fr_adam_flat(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), lp,
-                        (long)p.numel(), (float)lr, (float)b1, (float)b2, (float)eps, (float)bc1, (float)bc2,
-                        (float)grad_scale, cur_stream()),
+                        (long)p.numel(), (float)lr, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2),
+                        (float)eps, (float)bc1, (float)bc2, (float)grad_scale, cur_stream()),
            "adam_flat");
 }
 
