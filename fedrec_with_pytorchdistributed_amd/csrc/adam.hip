@@ -13,6 +13,7 @@
 // One streaming pass, float4 vectorised; optionally writes a bf16 copy of p (unfrozen
 // backbone: the compute weights are refreshed in the same pass).
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

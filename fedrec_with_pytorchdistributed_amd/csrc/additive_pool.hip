@@ -15,6 +15,7 @@
 // column sums) are reduced in LDS per block and stored to the block's own partial row; the
 // caller sums the rows with the deterministic colsum kernel (no float atomics).
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

@@ -11,6 +11,7 @@
 // construction), then a block-wide scan of the "new id" flags.  R <= 8192 (64 KB of keys);
 // larger batches take the sort-based torch path on the host side of the binding.
 #include "common.h"
+#include "launchers.h"
 
 #include <stdlib.h>
 

@@ -2,16 +2,20 @@
 
 * every ``*.hip`` kernel file -> ``hipcc --offload-arch=gfx950 -O3 -c`` (no torch headers,
   seconds per file, compiled in parallel);
-* ``binding.cpp`` (TORCH_LIBRARY registrations) -> host compile against torch's headers;
+* every ``*.cpp`` binding source (``bind_*.cpp``: a kernel family's op wrappers with their
+  TORCH_LIBRARY_FRAGMENT schemas and kernel registrations) -> host compile against torch's
+  headers, in parallel with the kernels;
 * link with the system linker against torch's *own* ``libamdhip64`` (rpath to torch/lib),
   so the process holds exactly one HIP runtime.
 
 Incremental: objects are rebuilt only when a source or any ``csrc/*.h`` header is newer (the
-headers carry layouts that several objects share, e.g. ``gemm_batch.h``).
+headers carry what several objects share: ``launchers.h`` the launcher ABI between the kernel
+files and the binding sources, ``gemm_batch.h`` a kernel-argument layout).  Only objects of the
+sources present are linked (a stale object of a source since removed is ignored).
 Usage: ``python -m fedrec_with_pytorchdistributed_amd.csrc.build [--force] [--verbose]``.
 
 ``--sanitize`` builds ``_C_san.so`` instead: the HOST code of every file
-(binding.cpp's argument checks and op glue, the IPC context table and handle plumbing of
+(the binding sources' argument checks and op glue, the IPC context table and handle plumbing of
 ipc_allreduce.hip, every launcher) under AddressSanitizer + UndefinedBehaviorSanitizer, with
 clang for every object so one sanitizer runtime serves them all (device code is not
 instrumented: ``-Xarch_host``).  It is never loaded by default; ``tests/test_sanitize_host.py``
@@ -70,7 +74,7 @@ def _run(cmd, verbose: bool):
 
 
 SAN = ["-fsanitize=address", "-fsanitize=undefined"]
-# binding.cpp only: no global-variable instrumentation -- its string literals were registered
+# binding sources only: no global-variable instrumentation -- their string literals were registered
 # twice at load (a false odr-violation report that ASAN_OPTIONS could not silence); heap, stack
 # and UB checks stay on (the .hip host objects keep the full instrumentation)
 SAN_CC = ["-mllvm", "-asan-globals=0"]
@@ -105,16 +109,15 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 8, sanitize: b
         if force or _newer(obj, [src, *common]):
             jobs_list.append([hipcc, f"--offload-arch={ARCH}", "-O3" if not sanitize else "-O1", "-fPIC", "-std=c++17",
                               "-munsafe-fp-atomics", *hsan, "-c", str(src), "-o", str(obj)])
-    bsrc = HERE / "binding.cpp"
-    bobj = bdir / "binding.o"
-    objs.append(bobj)
-    if force or _newer(bobj, [bsrc, *common]):
-        cxx, extra = ("g++", ["-O2"]) if not sanitize else (_clangxx(), ["-O1", *SAN, *SAN_CC,
-                                                                          "-fno-omit-frame-pointer"])
-        jobs_list.append([cxx, *extra, "-fPIC", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-DUSE_ROCM",
-                          f"-I{_rocm()}/include",
-                          f"-D_GLIBCXX_USE_CXX11_ABI={abi}", f"-I{tinc}", f"-I{tinc / 'torch/csrc/api/include'}",
-                          f"-I{sysconfig.get_paths()['include']}", "-c", str(bsrc), "-o", str(bobj)])
+    cxx, extra = ("g++", ["-O2"]) if not sanitize else (_clangxx(), ["-O1", *SAN, *SAN_CC, "-fno-omit-frame-pointer"])
+    for bsrc in sorted(HERE.glob("*.cpp")):
+        bobj = bdir / (bsrc.stem + ".o")
+        objs.append(bobj)
+        if force or _newer(bobj, [bsrc, *common]):
+            jobs_list.append([cxx, *extra, "-fPIC", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-DUSE_ROCM",
+                              f"-I{_rocm()}/include",
+                              f"-D_GLIBCXX_USE_CXX11_ABI={abi}", f"-I{tinc}", f"-I{tinc / 'torch/csrc/api/include'}",
+                              f"-I{sysconfig.get_paths()['include']}", "-c", str(bsrc), "-o", str(bobj)])
     if jobs_list:
         with cf.ThreadPoolExecutor(max_workers=max(1, min(jobs, len(jobs_list)))) as ex:
             for f in [ex.submit(_run, c, verbose) for c in jobs_list]:

@@ -20,8 +20,6 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 #define LDS_PTR(T, p) ((__attribute__((address_space(3))) T*)(p))
 #define GLOBAL_PTR(T, p) ((__attribute__((address_space(1))) T*)(p))
 
-#define FR_CHECK_LAUNCH() (void)0
-
 static __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
 static __device__ __forceinline__ float wave_sum(float v) {

@@ -10,6 +10,7 @@
 // so forward, backward and the torch oracle agree element for element.  One thread handles 8
 // consecutive bf16 (16-byte loads/stores, two Philox calls); a scalar tail covers n % 8.
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

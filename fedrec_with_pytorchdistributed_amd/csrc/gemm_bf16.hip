@@ -31,6 +31,7 @@
 // domain, 0 otherwise
 // (benchmarks/gemm_bench.py, profiles/r4_gemm_bench.json).
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

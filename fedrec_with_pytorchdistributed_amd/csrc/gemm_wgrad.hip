@@ -32,6 +32,7 @@
 //     one XCD's L2 (bijective blockIdx remap, §5.5 T1).
 // Requirements (host-checked): N % 8 == 0, K % 8 == 0 (16-B row chunks), contiguous rows.
 #include "common.h"
+#include "launchers.h"
 
 #include <stdlib.h>
 

@@ -34,6 +34,7 @@
 // at every epoch end, the bench).  All flag traffic is vector stores / loads with system-scope
 // ordering.
 #include "common.h"
+#include "launchers.h"
 
 #include <stdint.h>
 

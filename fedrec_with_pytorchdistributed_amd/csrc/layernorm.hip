@@ -9,6 +9,7 @@
 // (mean, then centred variance) from registers -- no extra memory pass.  HF uses the
 // biased variance and eps inside the sqrt (eps = 1e-12).
 #include "common.h"
+#include "launchers.h"
 
 #include <stdlib.h>
 

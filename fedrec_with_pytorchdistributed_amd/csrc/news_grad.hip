@@ -15,6 +15,7 @@
 // pass applies the clip + noise as it loads each occurrence row (one launch + the edge fix-up);
 // the separate per-occurrence pass (ldp_rows_kernel) remains for the other forms.
 #include "common.h"
+#include "launchers.h"
 
 #include <algorithm>
 

@@ -7,6 +7,7 @@
 // One wave per impression; the forward and the backward are one pass, so autograd's
 // backward is a scale by the incoming loss gradient.  Also used for validation scores.
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

@@ -9,6 +9,7 @@
 // exact.  PRG = Philox-4x32-10 keyed by the pair seed, counter =
 // (round, element).
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

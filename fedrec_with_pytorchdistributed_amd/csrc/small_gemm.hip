@@ -34,6 +34,7 @@
 // cycles).  A register queue two k-tiles deep (SG_NQ = 2) measured slower on every launch of
 // the config-2 step, even the ones with fewer tiles than CUs (profiles/r3_ab_sg_nq2.txt).
 #include "common.h"
+#include "launchers.h"
 #include "gemm_batch.h"
 
 #include <stdlib.h>
@@ -979,7 +980,7 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const ColsumBatch bat
 
 }  // namespace
 
-// descs: 8 pointers + 16 ints + 2 floats + 2 u64 per GEMM, packed by binding.cpp small_gemm.
+// descs: 8 pointers + 16 ints + 2 floats + 2 u64 per GEMM, packed by bind_user.cpp small_gemm.
 // scratch: split-K partial space (floats) the caller allocated; returns the floats it needs
 // when scratch is null (query mode).
 static int choose_splits(int tiles, int K, bool dma) {

@@ -27,9 +27,10 @@
 //                db1 = w2 sum g column sums; no dpre tensor exists.  w2[q] is applied to the
 //                fp32 result in the split-K reduction.
 //
-// Requirements (host-checked in binding.cpp): D % 256 == 0, Q in {128, 256, 384}, T <= 128 (T <= 96
+// Requirements (host-checked in bind_text_head.cpp): D % 256 == 0, Q in {128, 256, 384}, T <= 128 (T <= 96
 // at D = 1024).  Q = 384 (DistilBERT) takes the G path below; Q = 128 / 256 the round-4 head_wgrad.
 #include "common.h"
+#include "launchers.h"
 #include "gemm_batch.h"
 
 #include <stdlib.h>
@@ -1483,8 +1484,6 @@ extern "C" long fr_head_wgrad(const void* e, const void* table, const int* ids, 
                      dsump, db2p, w2, (f32x4*)dW1, db1, dw2, db2, S, Q, D, U, fr_sg::GemmBatch{}, 0, 0);
   return 0;
 }
-
-extern "C" int fr_small_gemm_batch_bytes();  // small_gemm.hip
 
 // ---- the G path (round 5) -------------------------------------------------------------------
 extern "C" int fr_head_g_supported(int D, int Q, int T) {

@@ -20,6 +20,7 @@
 // qkv: [n*T, 3*D] bf16 (q | k | v, head h at columns h*64 of each part); mask: [n, T] int32;
 // out: [n*T, D] bf16.
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 
@@ -655,9 +656,6 @@ int g_ta_cus = 0;
 }  // namespace
 
 extern "C" void fr_title_attn_set_waves(int w) { g_ta_waves = w; }
-
-extern "C" int fr_title_attention_long_bf16(const void* qkv, const int* mask, void* out, int n_titles, int T, int H,
-                                            int D, hipStream_t s);  // title_attn_long.hip, 64 < T <= 512
 
 extern "C" int fr_title_attention_bf16(const void* qkv, const int* mask, void* out, int n_titles, int T, int H, int D,
                                        hipStream_t s) {

@@ -16,6 +16,7 @@
 // all-masked <unk> row still passes gradient to V through its uniform P).
 // qkv/dqkv: [n*T, 3*D] bf16; dout: [n*T, D] bf16; mask: [n, T] int32.
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 
@@ -558,9 +559,6 @@ extern "C" void fr_title_attn_bwd_set_variant(int v) {
   if (v >= 10) g_tab_drop_split = v - 10;  // 10 / 11: the dropout backward's prefetch form
   else g_tab_variant = v;
 }
-
-extern "C" int fr_title_attention_bwd_long_bf16(const void* qkv, const void* dout, const int* mask, void* dqkv,
-                                                int n_titles, int T, int H, int D, hipStream_t s);  // title_attn_long.hip
 
 extern "C" int fr_title_attention_bwd_bf16(const void* qkv, const void* dout, const int* mask, void* dqkv,
                                            int n_titles, int T, int H, int D, hipStream_t s) {

@@ -11,6 +11,7 @@
 // u = sum_unmasked A dA k, w = sum_unmasked A k, D = sum_all A dA (dA = dO . v), keeping
 // (m, l, D) per row in LDS; pass B (lane = key) streams Q / dO chunks for dk, dv.
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

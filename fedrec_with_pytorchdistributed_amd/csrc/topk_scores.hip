@@ -37,6 +37,7 @@
 // topk_merge_kernel: one wave per user folds the S partial lists through the same sort (KP kept +
 //   a chunk of new keys per round) and decodes keys into (score, id).
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

@@ -8,6 +8,7 @@
 //               atomics; the pad token 0 -- most of the rows -- is skipped: nn.Embedding
 //               padding_idx keeps its gradient zero, so the index_add hot spot disappears)
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

@@ -15,6 +15,7 @@
 //
 // qkv: [B, H, 3*NH*DK] fp32 (q | k | v; head h at columns h*DK); ctx/dctx: [B, H, NH*DK].
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

@@ -273,7 +273,7 @@ def _refusals(dev, n):
 
 
 def test_adam_dev_refuses_bad_segments(dev):
-    """Every case is rejected by a host check (binding.cpp adam_dev, fr_adam_dev) before any
+    """Every case is rejected by a host check (bind_optim.cpp adam_dev, fr_adam_dev) before any
     launch: RuntimeError, and p, g, m, v as they were."""
     hp, lib = HPARAMS[0], native.lib()
     step = torch.ones(1, dtype=torch.int64, device=dev)
