@@ -263,7 +263,16 @@ __global__ __launch_bounds__(64 * WPB) void title_attn_bwd_kernel(const bf16* __
 // while it computes the current one from LDS.  All four operands are staged in LDS with a
 // 16-byte XOR swizzle (chunk ^ row & 7), so the MFMA fragments come from ds_read_b128
 // instead of a second round of global loads; V's buffer doubles as the P^T / dS^T scratch
-// once dP^T is formed.  Same math, same outputs as title_attn_bwd_kernel.
+// once dP^T is formed.  Same math as title_attn_bwd_kernel, and the same roundings wherever the
+// source fixes them: the MFMA operands, the bf16 roundings of P~ / dS, and hence dV, are bit-equal
+// between the forms.  D_t = sum_s P_ts dP_ts is not fixed by the source: hipcc contracts
+// a * b + c per term as it sees fit (-ffp-contract=fast), and it picks differently per
+// instantiation (the one-shot dropout kernel sums D_t with v_mul + v_add throughout, the
+// persistent dropout kernels fuse some terms into v_fma), so dQ and dK of the dropout forms can
+// differ from the one-shot's in a last bf16 bit (seen: 1-2 elements in 10^5).  Without dropout
+// the two forms compile to the same mix and their outputs are bit-equal; the split and unsplit
+// dropout forms are too.  tests/test_title_attention_oracle_gpu.py holds every form to the fp64
+// oracle on its own and asserts the equalities that do hold.
 struct TBIn {
   bf16x8 q[8], k[8], v[8], g[8];
   int mk;  // lane s: mask of key s (clamped row; s >= T is handled by the caller)
