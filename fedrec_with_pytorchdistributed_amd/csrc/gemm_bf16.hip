@@ -38,8 +38,10 @@ namespace {
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int STAGE_BYTES = (BM + BN) * BK * 2;  // 32 KB
 
-// GELU(erf) with erf from Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, far below bf16 output
-// rounding): one rcp + one exp + 6 FMA, no range branches (ocml erff costs ~3x in the epilogue).
+// GELU(erf) with erf from Abramowitz-Stegun 7.1.26: one rcp + one exp + 6 FMA, no range branches
+// (ocml erff costs ~3x in the epilogue).  A&S's |error| <= 1.5e-7 is for erf in exact arithmetic;
+// evaluated in fp32 the GELU forms below measure up to 1.9e-7 max(1, |x|) and GELU' up to 3.0e-7
+// (tests/gemm_oracle.py: EPS_MEASURED and its grid) -- still far below the bf16 output rounding.
 __device__ __forceinline__ float erf_fast(float x) {
   const float ax = fabsf(x);
   const float t = __frcp_rn(1.0f + 0.3275911f * ax);
@@ -51,7 +53,8 @@ __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + e
 
 // tanh(x) = 1 - 2 / (1 + e^{2x}): one exp2 + one rcp (ocml tanhf is a ~40-instruction
 // branchy routine in an epilogue that runs once per output element); saturates cleanly
-// (e^{2x} = inf -> 1, 0 -> -1); absolute error ~1e-7, far below the bf16 output rounding
+// (e^{2x} = inf -> 1, 0 -> -1); absolute error 1.8e-7 measured in fp32 (tests/gemm_oracle.py; no
+// relative accuracy near 0, where 1 - 2 / (1 + e) cancels), far below the bf16 output rounding
 __device__ __forceinline__ float tanh_fast(float x) {
   const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);  // 2 log2(e)
   return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + e);

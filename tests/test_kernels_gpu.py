@@ -1,6 +1,8 @@
 """Numerics of every HIP kernel against the plain-PyTorch fp32 oracle (ops/reference.py).
 
 bf16 kernels are compared with tolerances scaled to bf16 rounding; fp32 kernels tightly.
+The GEMM family (gemm_bf16.hip) is judged here by whole-output norms only; its per-element check
+against the fp64 oracle is tests/test_gemm_oracle_gpu.py.
 """
 import math
 
