@@ -326,6 +326,9 @@ __global__ __launch_bounds__(512, 1) void head_score2_kernel(const bf16* __restr
 //                   e^-m), masked tokens weight 0) in every wave (no barrier before the weights;
 //                   a token's weight reaches the lanes by shuffle), pooled = sum_t alpha_t x_t
 //                   (fp32) by TG t-groups x D / 8 column chunks, the t-group sums via LDS.
+//                   The form is stable for m >= -88.7 only: below, __expf(-m) is inf and every
+//                   alpha is 0 where the definition gives at most e^-88.7 / 1e-8 = 2.9e-31
+//                   (tests/head_oracle.py judges that edge absolutely).
 //   head_pool_bwd2  per title: dalpha_t = g . x_t, da_t = alpha_t (dalpha_t - sum alpha dalpha),
 //                   db2 partial = sum_t da_t; six waves over tokens t = w, w + 6, ..., the
 //                   per-token wave sums independent chains the compiler interleaves.
@@ -878,7 +881,8 @@ __global__ __launch_bounds__(512, 1) void head_wgrad_kernel(const bf16* __restri
 // dW1 = w2 (.) sum_s P[s] ; db1 = w2 (.) sum_s dsum[s] ; dw2 = sum_s dw2p[s] ; db2 = sum_u db2p[u]
 // (fixed summation order: deterministic).  A block owns 64 float4 of dW1: its 4 waves sum the
 // split partials s = w, w+4, ... (independent 16-B loads in flight per lane), then wave 0 adds
-// the 4 wave sums in order.  Then Q/64 blocks do dw2 / db1 the same way, the last block db2.
+// the 4 wave sums in order.  Then Q/64 blocks do dw2 / db1 the same way, the last block db2
+// (over every slot u < U, whatever nreal is: the pool backward writes db2p = 0 for padded titles).
 // PB: blocks from head_blocks on run a deferred small-GEMM split-K reduction (gemm_batch.h) --
 // the text FC backward's weight gradients, which nothing reads before the optimizer -- so that
 // reduction costs no launch of its own

@@ -2,7 +2,11 @@
 fp32 oracle of the reference head (encoder.py:27-29, attention.py:14-26): titles read from a
 hidden-state table by index (duplicates, padded slots of id 0, an all-padding title), forward
 (pooled) and every gradient (att_fc1 weight / bias, att_fc2 weight / bias), with and without the
-padding-token mask, T = 50 and shorter titles, and a row count that is not a tile multiple."""
+padding-token mask, T = 50 and shorter titles, and a row count that is not a tile multiple.
+
+These tests judge whole tensors by norm (end to end, at the training shapes); the per-element
+judgement of every launch against an fp64 oracle with counted bounds lives in
+tests/test_head_oracle_gpu.py (tests/head_oracle.py)."""
 import math
 
 import pytest
