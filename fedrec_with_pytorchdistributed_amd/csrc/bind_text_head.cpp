@@ -33,10 +33,7 @@ Tensor2 head_score(const at::Tensor& table, const OptTensor& ids, int64_t T, con
   // ids come from the dedup over [0, N) by construction)
   const c10::DeviceGuard g(table.device());
   auto e = store_e ? at::empty({U * T, Q}, table.options()) : at::empty({0}, table.options());
-  // [slices, U*T]: partial scores per Q slice of the tiling (summed by head_pool); 1 slice -> [U*T]
-  const int slices = fr_head_score_slices((int)Q);
-  auto a = slices > 1 ? at::empty({slices, U * T}, table.options().dtype(at::kFloat))
-                      : at::empty({U * T}, table.options().dtype(at::kFloat));
+  auto a = at::empty({U * T}, table.options().dtype(at::kFloat));
   check_rc(fr_head_score(table.data_ptr(), opt_int_ptr(ids), (int)U, (int)T, (int)D, (int)Q, w1.data_ptr(),
                          b1.data_ptr<float>(), w2.data_ptr<float>(), b2.data_ptr<float>(),
                          store_e ? e.data_ptr() : nullptr, a.data_ptr<float>(), opt_nreal(nreal, table), cur_stream()),
@@ -49,9 +46,7 @@ Tensor3 head_pool(const at::Tensor& table, const OptTensor& ids, int64_t T, cons
                   const OptTensor& nreal, bool want_bf16) {
   const int64_t U = head_titles(table, ids, T), D = table.size(1);
   check_dev(a, "a");
-  TORCH_CHECK(a.scalar_type() == at::kFloat && (a.numel() == U * T || (a.dim() == 2 && a.size(0) == 2 && a.size(1) == U * T)) &&
-                  a.is_contiguous(),
-              "fedrec::head_pool: a [U*T] (or [2, U*T] score partials) fp32");
+  TORCH_CHECK(a.scalar_type() == at::kFloat && a.numel() == U * T && a.is_contiguous(), "fedrec::head_pool: a [U*T] fp32");
   if (tokens.has_value()) {
     check_dev(*tokens, "tokens");
     TORCH_CHECK(tokens->scalar_type() == at::kInt && tokens->dim() == 3 && tokens->size(1) == 2 &&
@@ -62,9 +57,9 @@ Tensor3 head_pool(const at::Tensor& table, const OptTensor& ids, int64_t T, cons
   auto pooled = at::empty({U, D}, a.options());
   auto alpha = at::empty({U, T}, a.options());
   auto pooled_b = at::empty({want_bf16 ? U : 0, D}, a.options().dtype(at::kBFloat16));
-  check_rc(fr_head_pool(table.data_ptr(), opt_int_ptr(ids), a.data_ptr<float>(), a.dim() == 2 ? (int)a.size(0) : 1,
-                        opt_int_ptr(tokens), (int)U, (int)T, (int)D, pooled.data_ptr<float>(), alpha.data_ptr<float>(),
-                        opt_nreal(nreal, table), cur_stream(), want_bf16 ? pooled_b.data_ptr() : nullptr),
+  check_rc(fr_head_pool(table.data_ptr(), opt_int_ptr(ids), a.data_ptr<float>(), opt_int_ptr(tokens), (int)U, (int)T,
+                        (int)D, pooled.data_ptr<float>(), alpha.data_ptr<float>(), opt_nreal(nreal, table), cur_stream(),
+                        want_bf16 ? pooled_b.data_ptr() : nullptr),
            "head_pool");
   return {pooled, alpha, pooled_b};
 }
@@ -298,7 +293,6 @@ Tensor4 upool_bwd_da(const at::Tensor& x, const at::Tensor& e, const at::Tensor&
 TORCH_LIBRARY_FRAGMENT(fedrec, m) {
   m.def("head_score_set_rows(int r) -> ()", [](int64_t r) { fr_head_score_set_rows((int)r); });
   m.def("head_score_set_ilv(int v) -> ()", [](int64_t v) { fr_head_score_set_ilv((int)v); });
-  m.def("head_wgrad_g_set_kt(int kt) -> ()", [](int64_t kt) { fr_head_wgrad_g_set_kt((int)kt); });
   m.def("head_supported(int D, int Q, int T) -> bool",
         [](int64_t D, int64_t Q, int64_t T) { return fr_head_supported((int)D, (int)Q, (int)T) != 0; });
   m.def("head_g_supported(int D, int Q, int T) -> bool",

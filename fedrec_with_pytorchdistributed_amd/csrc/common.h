@@ -49,6 +49,15 @@ static __device__ __forceinline__ float group4_max(float v) {
 static __device__ __forceinline__ float bf2f(bf16 x) { return (float)x; }
 static __device__ __forceinline__ bf16 f2bf(float x) { return (bf16)x; }
 
+// tanh(x) = 1 - 2 / (1 + e^{2x}): one exp2 + one rcp (ocml tanhf is a ~40-instruction
+// branchy routine in an epilogue that runs once per output element); saturates cleanly
+// (e^{2x} = inf -> 1, 0 -> -1); absolute error 1.8e-7 measured in fp32 (tests/gemm_oracle.py; no
+// relative accuracy near 0, where 1 - 2 / (1 + e) cancels), far below the bf16 output rounding
+static __device__ __forceinline__ float tanh_fast(float x) {
+  const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);  // 2 log2(e)
+  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + e);
+}
+
 // ---------------------------------------------------------------------------------------
 // Philox-4x32-10 (Salmon et al. 2011); counter = (offset, idx), key = seed.
 struct Philox {

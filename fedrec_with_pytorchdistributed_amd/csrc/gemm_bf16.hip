@@ -51,15 +51,6 @@ __device__ __forceinline__ float erf_fast(float x) {
 }
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erf_fast(x * 0.70710678118654752f)); }
 
-// tanh(x) = 1 - 2 / (1 + e^{2x}): one exp2 + one rcp (ocml tanhf is a ~40-instruction
-// branchy routine in an epilogue that runs once per output element); saturates cleanly
-// (e^{2x} = inf -> 1, 0 -> -1); absolute error 1.8e-7 measured in fp32 (tests/gemm_oracle.py; no
-// relative accuracy near 0, where 1 - 2 / (1 + e) cancels), far below the bf16 output rounding
-__device__ __forceinline__ float tanh_fast(float x) {
-  const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);  // 2 log2(e)
-  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + e);
-}
-
 template <int ACT>
 __device__ __forceinline__ float act_fn(float x) {
   if constexpr (ACT == 1) return gelu_erf(x);
@@ -1001,19 +992,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_pp3_kernel(const bf16* __restr
   if (wr == 0) pp_barrier();
 }
 
-int g_num_cus = 0;
-
 int g_gemm_variant = -1;  // -1 auto; 0 = 128x128, 6 / 9 / 12 / 13 = the ping-pong forms (A/B runs)
-
-static int num_cus() {
-  if (g_num_cus == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&g_num_cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (g_num_cus <= 0) g_num_cus = 256;
-  }
-  return g_num_cus;
-}
 
 // the ping-pong kernels' domain: 256x256 tiles (a partial last column tile only in variant 9),
 // C rows padded to a multiple of 256 (unpredicated stores), 32-bit operand offsets
@@ -1037,7 +1016,7 @@ void launch_act(const bf16* A, const bf16* W, const float* bias, const bf16* R, 
   const bool big = (auto_v && (N % BN2 == 0 || part_n) && M >= 4096) || (g_gemm_variant >= 6 && (N % BN2 == 0 || part_n));
   if (big && (auto_v || g_gemm_variant == 9 || g_gemm_variant >= 12) && pp_domain(M, N, K, c_rows)) {
     const int tiles_n = (N + BN2 - 1) / BN2, tiles_m = (M + BM2 - 1) / BM2, ntiles = tiles_m * tiles_n;
-    const int G = ntiles < num_cus() ? ntiles : num_cus();
+    const int G = ntiles < fr_num_cus() ? ntiles : fr_num_cus();
     // auto: variant 13 (bias-armed accumulators, non-temporal stores) on the no-residual shapes
     // with K < 2048; variant 9 for the rest (residual / GELU-backward epilogues, FFN2)
     if constexpr (ACT != 3) {
@@ -1079,7 +1058,7 @@ void launch_act(const bf16* A, const bf16* W, const float* bias, const bf16* R, 
   // stores) while the 32-bit offsets hold, else the 128x128 kernel (64-bit addressing)
   if (big && N % BN2 == 0 && K >= 128 && (long long)M * K < (1ll << 31) && (long long)N * K < (1ll << 31)) {
     const int tiles_n = N / BN2, tiles_m = (M + BM2 - 1) / BM2, ntiles = tiles_m * tiles_n;
-    const int G = ntiles < num_cus() ? ntiles : num_cus();
+    const int G = ntiles < fr_num_cus() ? ntiles : fr_num_cus();
 #define LPP(HB, HR)                                                                                        \
   hipLaunchKernelGGL((gemm_nt_pp_kernel<ACT, HB, HR>), dim3(G), dim3(512), 0, s, A, W, bias, R, C, M, N, K, tiles_n, \
                      ntiles)
@@ -1099,6 +1078,17 @@ void launch_act(const bf16* A, const bf16* W, const float* bias, const bf16* R, 
 }
 
 }  // namespace
+
+extern "C" int fr_num_cus() {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (cus <= 0) cus = 256;
+  }
+  return cus;
+}
 
 extern "C" void fr_gemm_set_variant(int v) { g_gemm_variant = v; }
 
@@ -1136,7 +1126,7 @@ extern "C" int fr_gemm_nt_bf16_split(const void* A, const void* W, const float* 
                   n_partial % BN2 == 0 && n_partial > 0 && n_partial <= N && pp_domain(M, N, K, c_rows);
   if (!ok) return fr_gemm_nt_bf16(A, W, bias, nullptr, C, M, N, K, 0, c_rows, s);
   const int tiles_n = N / BN2, tiles_m = (M + BM2 - 1) / BM2, ntiles_max = tiles_m * tiles_n;
-  const int G = ntiles_max < num_cus() ? ntiles_max : num_cus();
+  const int G = ntiles_max < fr_num_cus() ? ntiles_max : fr_num_cus();
   const bf16* a = (const bf16*)A;
   const bf16* w = (const bf16*)W;
   bf16* c = (bf16*)C;
@@ -1169,7 +1159,7 @@ extern "C" int fr_gemm_gelu_bwd_colpart(const void* A, const void* W, const void
                   K % BK == 0 && pp_domain(M, N, K, c_rows);
   if (!ok) return 3;
   const int tiles_n = N / BN2, tiles_m = (M + BM2 - 1) / BM2, ntiles = tiles_m * tiles_n;
-  const int G = ntiles < num_cus() ? ntiles : num_cus();
+  const int G = ntiles < fr_num_cus() ? ntiles : fr_num_cus();
   hipLaunchKernelGGL((gemm_nt_pp2_kernel<3, false, true>), dim3(G), dim3(512), 0, s, (const bf16*)A, (const bf16*)W,
                      nullptr, (const bf16*)Z, (bf16*)C, M, N, K, tiles_n, ntiles, nullptr, 0, nullptr, colpart);
   return 0;
@@ -1181,7 +1171,7 @@ extern "C" int fr_gemm_nt_bf16_dual(const void* A, const void* W, const float* b
                   K % BK == 0 && bias != nullptr && pp_domain(M, N, K, c_rows);
   if (!ok) return 3;
   const int tiles_n = N / BN2, tiles_m = (M + BM2 - 1) / BM2, ntiles = tiles_m * tiles_n;
-  const int G = ntiles < num_cus() ? ntiles : num_cus();
+  const int G = ntiles < fr_num_cus() ? ntiles : fr_num_cus();
   if (g_gemm_variant != 9 && (g_gemm_variant >= 12 || M < (1 << 18))) {
     hipLaunchKernelGGL((gemm_nt_pp3_kernel<1, true, true, true>), dim3(G), dim3(512), 0, s, (const bf16*)A, (const bf16*)W,
                        bias, (bf16*)C, M, N, K, tiles_n, ntiles, nullptr, 0, (bf16*)Z);

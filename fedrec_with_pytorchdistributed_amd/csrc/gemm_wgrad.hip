@@ -33,6 +33,7 @@
 // Requirements (host-checked): N % 8 == 0, K % 8 == 0 (16-B row chunks), contiguous rows.
 #include "common.h"
 #include "launchers.h"
+#include "tn_pipe.h"
 
 #include <stdlib.h>
 
@@ -43,8 +44,6 @@ constexpr int OP_BYTES = TM * 512;                 // one operand tile: 32 rows 
 constexpr int WSTAGE = 2 * OP_BYTES;               // 32 KB
 
 __device__ __attribute__((aligned(16))) bf16 g_zero_row[256];  // zero-initialised (bss)
-
-__device__ __forceinline__ int swz(int row) { return ((row & 3) | (((row >> 3) & 1) << 2)) << 1; }
 
 // 32 rows x 256 columns of a row-major [rows, ld] operand into `dst` (swizzled): 16 glds of
 // 1 KB (2 rows each), 2 per wave
@@ -63,33 +62,6 @@ __device__ __forceinline__ void stage_op(char* dst, const bf16* __restrict__ src
   }
 }
 
-// LDS byte offset of this lane's 8 bytes for a transposed read of rows r0 + q (q = 0..3),
-// columns col0 + 4p .. +3 (lane 4q+p of its 16-lane group)
-__device__ __forceinline__ uint32_t tr_off(int r0, int col0, int q, int p) {
-  const int c = (col0 >> 3) + (p >> 1);
-  const int r = r0 + q;
-  return (uint32_t)(r * 512 + ((c ^ swz(r)) << 4) + (p & 1) * 8);
-}
-
-// ds_read_b64_tr_b16 as opaque asm: a plain (builtin) LDS read after a glds into the same LDS
-// object makes the compiler drain vmcnt first -- every in-flight stage -- which serialises the
-// pipeline.  The reads' completion is then ours to wait for (lgkm_tie*).
-__device__ __forceinline__ s16x4 tr_read(uint32_t addr) {
-  s16x4 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
-  return v;
-}
-
-#define LGKM_TIE8(r)                                                                                  \
-  asm volatile("s_waitcnt lgkmcnt(0)"                                                                 \
-               : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), \
-                 "+v"(r[7]))
-
-__device__ __forceinline__ bf16x8 join(s16x4 a, s16x4 b) {
-  bf16x4 x = __builtin_bit_cast(bf16x4, a), y = __builtin_bit_cast(bf16x4, b);
-  return bf16x8{x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
-}
-
 __device__ __forceinline__ void sync_stage(int inflight) {  // inflight younger stages may stay
   __builtin_amdgcn_sched_barrier(0);
   if (inflight >= 3) asm volatile("s_waitcnt vmcnt(12)\n\ts_barrier" ::: "memory");
@@ -105,9 +77,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_kernel(const bf16* __restrict__ 
                                                        float* __restrict__ P, int M, int N, int K, int tiles_k,
                                                        int ntiles, int mchunk) {
   __shared__ __attribute__((aligned(16))) char smem[NST * WSTAGE];
-  const int bid = blockIdx.x, nwg = gridDim.x;
-  const int xcd = bid & 7, qq = nwg >> 3, rmd = nwg & 7;
-  const int t = (xcd < rmd ? xcd * (qq + 1) : rmd * (qq + 1) + (xcd - rmd) * qq) + (bid >> 3);
+  const int t = xcd_block(blockIdx.x, gridDim.x);
   const int s = t / ntiles, tile = t - s * ntiles;
   const int nt = tile / tiles_k, kt = tile - nt * tiles_k;
   const int n0 = nt * TN, k0 = kt * TKO;
@@ -137,13 +107,13 @@ __global__ __launch_bounds__(512, 1) void wgrad_kernel(const bf16* __restrict__ 
   uint32_t xo[4][2], yo[8][2];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    xo[j][0] = OP_BYTES + tr_off(r0, wk * 64 + j * 16, q, p);
-    xo[j][1] = OP_BYTES + tr_off(r0 + 4, wk * 64 + j * 16, q, p);
+    xo[j][0] = OP_BYTES + tr_off(512, r0, wk * 64 + j * 16, q, p);
+    xo[j][1] = OP_BYTES + tr_off(512, r0 + 4, wk * 64 + j * 16, q, p);
   }
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    yo[i][0] = tr_off(r0, wn * 128 + i * 16, q, p);
-    yo[i][1] = tr_off(r0 + 4, wn * 128 + i * 16, q, p);
+    yo[i][0] = tr_off(512, r0, wn * 128 + i * 16, q, p);
+    yo[i][1] = tr_off(512, r0 + 4, wn * 128 + i * 16, q, p);
   }
   const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(char, smem);
   for (int st = 0; st < nsteps; ++st) {
@@ -223,19 +193,11 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const f32x4* __restri
   }
 }
 
-int g_cus = 0;
-
 void plan(int M, int N, int K, int& S, int& mchunk, int& ntiles, int& tiles_k) {
-  if (g_cus == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&g_cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (g_cus <= 0) g_cus = 256;
-  }
   tiles_k = (K + TKO - 1) / TKO;
   ntiles = ((N + TN - 1) / TN) * tiles_k;
   // one wave of workgroups (one block per CU), each split >= 8 reduction steps
-  int s = g_cus / ntiles;
+  int s = fr_num_cus() / ntiles;
   const int smax = (M + 16 * TM - 1) / (16 * TM);
   s = s < 1 ? 1 : (s > smax ? smax : s);
   const int rows = (M + s - 1) / s;

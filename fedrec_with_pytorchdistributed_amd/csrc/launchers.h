@@ -11,6 +11,7 @@
 extern "C" {
 
 // ---- gemm_bf16.hip ---------------------------------------------------------------------------
+int fr_num_cus();  // the current device's CU count, queried once (256 if the query fails); every file's grid sizing
 void fr_gemm_set_variant(int v);
 int fr_gemm_nt_bf16(const void* A, const void* W, const float* bias, const void* R, void* C, int M, int N, int K, int act,
                     int c_rows, hipStream_t s);
@@ -80,14 +81,12 @@ int fr_embed_grad_bf16(const void* dx, const int* sorted, const int* perm, int R
 // ---- text_head.hip ---------------------------------------------------------------------------
 void fr_head_score_set_rows(int r);
 void fr_head_score_set_ilv(int v);
-void fr_head_wgrad_g_set_kt(int kt);
 int fr_head_supported(int D, int Q, int T);
 int fr_head_g_supported(int D, int Q, int T);
-int fr_head_score_slices(int Q);
 int fr_head_score(const void* table, const int* ids, int U, int T, int D, int Q, const void* W1, const float* b1,
                   const float* w2, const float* b2, void* e_out, float* a_out, const int* nreal, hipStream_t s);
-int fr_head_pool(const void* table, const int* ids, const float* a, int slices, const int* tokens, int U, int T, int D,
-                 float* pooled, float* alpha, const int* nreal, hipStream_t s, void* pooled_b);
+int fr_head_pool(const void* table, const int* ids, const float* a, const int* tokens, int U, int T, int D, float* pooled,
+                 float* alpha, const int* nreal, hipStream_t s, void* pooled_b);
 int fr_head_pool_bwd(const void* table, const int* ids, const float* alpha, const float* g, int U, int T, int D,
                      float* da, float* db2p, const int* nreal, hipStream_t s);
 long fr_head_wgrad(const void* e, const void* table, const int* ids, const float* da, const float* db2p,

@@ -271,17 +271,9 @@ __global__ __launch_bounds__(256) void ln16p_kernel(const bf16* __restrict__ x, 
   }
 }
 
-int g_ln_cus = 0;
-
 bool launch_ln16p(const bf16* x, const float* w, const float* b, bf16* y, int rows, int D, float eps, hipStream_t s,
                   const bf16* res, const int* ridx) {
-  if (g_ln_cus == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&g_ln_cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (g_ln_cus <= 0) g_ln_cus = 256;
-  }
-  int blocks = g_ln_cus * 8;
+  int blocks = fr_num_cus() * 8;
   const int need = (rows + 7) / 8;
   blocks = blocks < need ? blocks : need;
   if (D == 768)

@@ -10,28 +10,37 @@
 // and a step needs the U ~ 1.6k unique titles of its batch.  Round 2 materialised them with a
 // gather (128 MB), ran att_fc1 as a plain GEMM that wrote e (64 MB), re-read x and e in the pool,
 // wrote dpre = da w2 (1 - e^2) (64 MB) in the pool backward and re-read dpre and x in the weight
-// gradient: ~290 us of the 0.8 ms step was the same rows going through HBM five times.  Here:
+// gradient: ~290 us of the 0.8 ms step was the same rows going through HBM five times.  Here
+// every kernel reads its X rows straight from the cache by title index, and neither a gathered
+// copy nor a dpre tensor exists.  One form per kernel (what the others measured is in
+// docs/PERFORMANCE.md):
 //
-//   head_score   A rows loaded straight from the cache by title index (row m -> cache row
-//                ids[m / T] * T + m % T, per-lane glds source address), the whole Q = 384 in
-//                one block (128 x 384 tile, 8 waves) so the epilogue forms the score
-//                a_m = w2 . tanh(acc + b1) + b2 in registers (cross-lane + LDS reduction);
-//                e is stored once in bf16 for the backward.
-//   head_pool    per title: eps-softmax of a (optional token mask) and pooled = sum alpha x
-//                (x read through the same index).
-//   head_pool_bwd  per title: dalpha_t = g . x_t, da_t = alpha_t (dalpha_t - sum alpha dalpha).
-//   head_wgrad   dW1[q][k] = w2[q] sum_m da_m (1 - e_mq^2) x_mk: a split-K TN MFMA GEMM whose
-//                dY operand is FORMED IN ITS LDS PIPELINE -- the raw e tile and the da values
-//                arrive by glds, one pass per stage rewrites the e tile in place as
-//                g = da (1 - e^2) (bf16) while accumulating the dw2 = sum da e and
-//                db1 = w2 sum g column sums; no dpre tensor exists.  w2[q] is applied to the
-//                fp32 result in the split-K reduction.
+//   head_score2_kernel    (every Q) the score GEMM: the whole Q in one block, so the epilogue
+//       forms a_m = w2 . tanh(acc + b1) + b2 in registers; e is stored once in bf16 for the
+//       backward.  Row tile 160 or 192 at Q = 384 (by the rounds rule in fr_head_score, the next
+//       stage's loads interleaved with the MFMA rows or not), 128 at Q = 128 / 256.
+//   head_pool2_kernel     (every Q) per title: eps-softmax of a (optional token mask) and
+//       pooled = sum alpha x.
+//   head_pool_bwd2_kernel (Q = 128 / 256) per title: dalpha_t = g . x_t,
+//       da_t = alpha_t (dalpha_t - sum alpha dalpha), the db2 partial.
+//   head_wgrad_kernel     (Q = 128 / 256) dW1[q][k] = w2[q] sum_m da_m (1 - e_mq^2) x_mk: a
+//       split-K TN MFMA GEMM whose dY operand is formed in its LDS pipeline -- the raw e tile
+//       and the da values arrive by glds and the e tile is rewritten in place as
+//       g = da (1 - e^2) (bf16) while the dw2 = sum da e and db1 = w2 sum g column sums
+//       accumulate.
+//   head_pool_bwd3_kernel (Q = 384, the G path) head_pool_bwd2 that also rewrites the title's
+//       e rows as g in place and writes its column partials.
+//   head_wgrad_g_kernel   (Q = 384, the G path) the weight gradient as a plain split-K TN MFMA
+//       GEMM over the ready g rows and the cached X rows.
+//   head_reduce_kernel    (every Q) sums the split-K partials in a fixed order and applies
+//       w2[q]; on the G path a deferred small-GEMM reduction can ride in its launch.
 //
-// Requirements (host-checked in bind_text_head.cpp): D % 256 == 0, Q in {128, 256, 384}, T <= 128 (T <= 96
-// at D = 1024).  Q = 384 (DistilBERT) takes the G path below; Q = 128 / 256 the round-4 head_wgrad.
+// Requirements (host-checked in bind_text_head.cpp): D % 256 == 0, Q in {128, 256, 384},
+// T <= 128 (T <= 96 at D = 1024).
 #include "common.h"
 #include "launchers.h"
 #include "gemm_batch.h"
+#include "tn_pipe.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -41,11 +50,6 @@
 namespace {
 
 constexpr int MAXT = 128;
-
-__device__ __forceinline__ float tanh_fast(float x) {  // 1 - 2 / (1 + e^{2x}), as gemm_bf16.hip
-  const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);
-  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + e);
-}
 
 __device__ __attribute__((aligned(16))) bf16 g_zero_row[512];  // zero-initialised (bss)
 __device__ float g_zero_f32[64];
@@ -72,39 +76,29 @@ __device__ __forceinline__ u32x4_t lds_read128(uint32_t addr) {
 // head_score2: e = tanh(X W1^T + b1) (bf16, optional), a = e . w2 + b2 (fp32, from the fp32 e).
 // The A rows come straight from the cache by title index (row m -> cache row ids[m / T] * T +
 // m % T, per-lane glds source addresses); the whole Q sits in one block, so the epilogue forms
-// the score in registers (cross-lane + LDS reduction).  512 threads = 8 waves as WMN (rows) x
-// WQ (columns), v_mfma_f32_16x16x32_bf16 with W1 as the A operand (a lane ends with 4
-// consecutive columns of one row).  The row tile (32 RF rows), the k-tile (BK) and the depth
-// of the LDS pipeline (NST stages, NST - 2 in flight while the MFMAs read one) are parameters.
-// A stage is XP + WP "pieces" of one wave-instruction each (64 lanes x 16 B = RPP rows of BK
+// the score in registers (cross-lane + LDS reduction).  512 threads = 8 waves as 2 (rows) x
+// 4 (columns), v_mfma_f32_16x16x32_bf16 with W1 as the A operand (a lane ends with 4
+// consecutive columns of one row).  The row tile is the parameter (32 RF rows); the k-tile is
+// 64 and the LDS pipeline two stages, one in flight while the MFMAs read the other (the other
+// k-tiles, depths and wave grids measured: docs/PERFORMANCE.md).
+// A stage is XP + WP "pieces" of one wave-instruction each (64 lanes x 16 B = 8 rows of 64
 // bf16); wave w issues pieces w, w + 8, ... and pads to PPW pieces with duplicates of the
-// first ones (identical bytes to the same LDS address), so every wave counts the same glds per
-// stage and the waits are counted (vmcnt) rather than drains.  LDS reads are opaque asm (a
-// builtin LDS read after a glds makes the compiler drain vmcnt).  Rows of BK = 32 stages are
-// 64 B: chunk c of row r at c ^ ((r >> 2) & 3) keeps a 16-lane ds_read_b128 group on 64
-// distinct banks; BK = 64 rows are 128 B with chunk c of row r at c ^ (r & 7) (conflict-free
-// ds_read_b128; glds images are lane-linear so the XOR goes on the source).
+// first ones (identical bytes to the same LDS address), so every wave issues the same glds per
+// stage.  LDS reads are opaque asm (a builtin LDS read after a glds makes the compiler drain
+// vmcnt).  Rows are 128 B with chunk c of row r at c ^ (r & 7) (conflict-free ds_read_b128;
+// glds images are lane-linear so the XOR goes on the source).
+// The LDS waits are staged: the X fragments are read first, then the W1 fragments in MFMA-row
+// order, and row i of the MFMAs waits only for W1 fragment i (lgkmcnt QFW - 1 - i), as
+// head_wgrad's.
 // -----------------------------------------------------------------------------------------
-template <int BK>
-__device__ __forceinline__ int hs_swz(int r) {
-  return BK == 64 ? (r & 7) : ((r >> 2) & 3);
-}
+__device__ __forceinline__ int hs_swz(int r) { return r & 7; }
 
-template <int N>
-__device__ __forceinline__ void hs_wait_sync() {  // this wave's stage landed except N younger glds, then barrier
+__device__ __forceinline__ void hs_wait_sync() {  // every glds and LDS read of this wave done, then barrier
   __builtin_amdgcn_sched_barrier(0);
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
 }
 
-//
-// Q slices (gridDim.y > 1): block (x, y) computes columns [y Q, (y + 1) Q) of e (row stride ldq)
-// and the partial score sum_{q in slice} w2_q tanh(.) into a_out[y M + m] (b2 in slice 0); the
-// pool adds the slices.  Halving the W1 panel per block (192 of 384 columns) frees the LDS for a
-// third stage: two stages in flight while the MFMAs read one.
-// SW: staged LDS waits -- the X fragments first, then the W1 fragments in MFMA-row order, and
-// row i of the MFMAs waits only for W1 fragment i (lgkmcnt QFW - 1 - i), as head_wgrad's SW.
 template <int N>
 __device__ __forceinline__ void lgkm_tie(u32x4_t& r) {
   asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(r) : "n"(N));
@@ -122,30 +116,22 @@ __device__ __forceinline__ void lgkm_tie_rt(int n, u32x4_t& r) {  // n folds to 
   }
 }
 
-// ILV (with SW): the next stage's PPW glds pieces are issued between the MFMA rows of this
+// ILV: the next stage's PPW glds pieces are issued between the MFMA rows of this
 // stage (one per row) instead of all at once after the barrier -- an LDS-DMA piece costs ~60-185
 // issue cycles (MI355X_MICROARCH.md, per-instruction table), ~1,000 per wave per stage that
 // otherwise sit between the barrier and the first MFMA.  Standalone (benchmarks/head_bench.py,
 // 1600 titles): 192-row tiles 78.0 -> 67.4 us, 160-row tiles 64.8 -> 61.1 us; inside the step
 // graph neutral (0.4414 vs 0.4414 ms, profiles/r6_ab_head_ilv.jsonl).  The default; the plain
 // form stays for the bitwise test (head_score_set_ilv(0)).
-template <int QF, int RF, int BK, int NST, int WQ = 4, bool SW = false, bool ILV = false>
+template <int QF, int RF, bool ILV = false>
 __global__ __launch_bounds__(512, 1) void head_score2_kernel(const bf16* __restrict__ table, const int* __restrict__ ids,
                                                              int M, int T, int D, const bf16* __restrict__ W1,
                                                              const float* __restrict__ b1, const float* __restrict__ w2,
                                                              const float* __restrict__ b2, bf16* __restrict__ e_out,
-                                                             float* __restrict__ a_out, int ldq,
-                                                             const int* __restrict__ nreal) {
+                                                             float* __restrict__ a_out, const int* __restrict__ nreal) {
   constexpr int Q = QF * 64;
-  {
-    const int qs = blockIdx.y;
-    W1 += (size_t)qs * Q * D;
-    b1 += qs * Q;
-    w2 += qs * Q;
-    if (e_out != nullptr) e_out += qs * Q;
-    a_out += (size_t)qs * M;
-  }
-  const float b2v = blockIdx.y == 0 ? b2[0] : 0.f;
+  constexpr int BK = 64, NST = 2, WQ = 4;  // k-tile, LDS stages, waves along the columns
+  const float b2v = b2[0];
   constexpr int MR = 32 * RF;       // rows per block
   constexpr int RB = BK * 2;        // LDS row bytes
   constexpr int CPR = BK / 8;       // 16-B chunks per row
@@ -178,11 +164,11 @@ __global__ __launch_bounds__(512, 1) void head_score2_kernel(const bf16* __restr
         const int r = p * RPP + lr;
         int gm = m0 + r;
         gm = gm < M ? gm : M - 1;  // rows past M: any valid row (outputs masked)
-        src[i] = hrow(table, ids, gm, T, D) + (pc ^ hs_swz<BK>(r)) * 8;
+        src[i] = hrow(table, ids, gm, T, D) + (pc ^ hs_swz(r)) * 8;
         dst[i] = (uint32_t)(p * RPP * RB);
       } else {
         const int r = (p - XP) * RPP + lr;
-        src[i] = W1 + (size_t)r * D + (pc ^ hs_swz<BK>(r)) * 8;
+        src[i] = W1 + (size_t)r * D + (pc ^ hs_swz(r)) * 8;
         dst[i] = (uint32_t)((MR + (p - XP) * RPP) * RB);
       }
     }
@@ -199,7 +185,7 @@ __global__ __launch_bounds__(512, 1) void head_score2_kernel(const bf16* __restr
                                      LDS_PTR(void, smem + stage * ST + dst[i]), 16, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
   };
-  static_assert(!ILV || (SW && PPW <= KS * QFW), "interleaved issue: one piece per MFMA row");
+  static_assert(!ILV || PPW <= KS * QFW, "interleaved issue: one piece per MFMA row");
 
   f32x4 acc[QFW][RFW];
 #pragma unroll
@@ -214,10 +200,7 @@ __global__ __launch_bounds__(512, 1) void head_score2_kernel(const bf16* __restr
   const int fr = lane & 15, fq = lane >> 4;
   for (int kt = 0; kt < nk; ++kt) {
     // stage kt landed (every wave), every wave done with stage kt - 1
-    const int younger = nk - 1 - kt;  // stages issued after kt, at most NST - 2
-    if (NST >= 4 && younger >= 2) hs_wait_sync<(NST >= 4 ? 2 * PPW : 0)>();
-    else if (NST >= 3 && younger >= 1) hs_wait_sync<(NST >= 3 ? PPW : 0)>();
-    else hs_wait_sync<0>();
+    hs_wait_sync();
     const bool nxt = kt + NST - 1 < nk;
     const int nst = (kt + NST - 1) % NST, nk0 = (kt + NST - 1) * BK;
     if (!ILV && nxt) issue(nst, nk0);
@@ -229,47 +212,31 @@ __global__ __launch_bounds__(512, 1) void head_score2_kernel(const bf16* __restr
 #pragma unroll
       for (int j = 0; j < RFW; ++j) {
         const int r = wm * 16 * RFW + j * 16 + fr;
-        xr[j] = lds_read128(As + r * RB + ((lc ^ hs_swz<BK>(r)) << 4));
+        xr[j] = lds_read128(As + r * RB + ((lc ^ hs_swz(r)) << 4));
       }
 #pragma unroll
       for (int i = 0; i < QFW; ++i) {
         const int r = wq * QFW * 16 + i * 16 + fr;
-        wr[i] = lds_read128(Ws + r * RB + ((lc ^ hs_swz<BK>(r)) << 4));
+        wr[i] = lds_read128(Ws + r * RB + ((lc ^ hs_swz(r)) << 4));
       }
-      if constexpr (SW) {
-        static_assert(QFW <= 8, "lgkmcnt staging");
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < QFW; ++i) {
-          lgkm_tie_rt(QFW - 1 - i, wr[i]);  // X fragments (issued first) and W1 fragment i landed
-          if (i == 0) {
-#pragma unroll
-            for (int j = 0; j < RFW; ++j) asm volatile("" : "+v"(xr[j]));
-          }
-#pragma unroll
-          for (int j = 0; j < RFW; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wr[i]),
-                                                                __builtin_bit_cast(bf16x8, xr[j]), acc[i][j], 0, 0, 0);
-          if constexpr (ILV) {
-            const int pc_ = kk * QFW + i;
-            if (pc_ < PPW && nxt) issue_one(pc_, nst, nk0);
-          }
-        }
-        __builtin_amdgcn_s_setprio(0);
-        continue;
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int j = 0; j < RFW; ++j) asm volatile("" : "+v"(xr[j]));  // uses stay after the wait
-#pragma unroll
-      for (int i = 0; i < QFW; ++i) asm volatile("" : "+v"(wr[i]));
+      static_assert(QFW <= 8, "lgkmcnt staging");
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int i = 0; i < QFW; ++i)
+      for (int i = 0; i < QFW; ++i) {
+        lgkm_tie_rt(QFW - 1 - i, wr[i]);  // X fragments (issued first) and W1 fragment i landed
+        if (i == 0) {
+#pragma unroll
+          for (int j = 0; j < RFW; ++j) asm volatile("" : "+v"(xr[j]));
+        }
 #pragma unroll
         for (int j = 0; j < RFW; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wr[i]),
                                                               __builtin_bit_cast(bf16x8, xr[j]), acc[i][j], 0, 0, 0);
+        if constexpr (ILV) {
+          const int pc_ = kk * QFW + i;
+          if (pc_ < PPW && nxt) issue_one(pc_, nst, nk0);
+        }
+      }
       __builtin_amdgcn_s_setprio(0);
     }
   }
@@ -299,7 +266,7 @@ __global__ __launch_bounds__(512, 1) void head_score2_kernel(const bf16* __restr
 #pragma unroll
       for (int j = 0; j < RFW; ++j) {
         const int m = m0 + wm * 16 * RFW + j * 16 + fr;
-        store_pair16_if(e_out + (size_t)(m < M ? m : 0) * ldq + wq * QFW * 16 + i * 16, v[0][j], v[1][j], fq, m < M);
+        store_pair16_if(e_out + (size_t)(m < M ? m : 0) * Q + wq * QFW * 16 + i * 16, v[0][j], v[1][j], fq, m < M);
       }
     }
   }
@@ -310,12 +277,9 @@ __global__ __launch_bounds__(512, 1) void head_score2_kernel(const bf16* __restr
     if (fq == 0) red[wq * MR + wm * 16 * RFW + j * 16 + fr] = s;
   }
   __syncthreads();
-  if (tid < MR && m0 + tid < M) {
-    float sa;
-    if constexpr (WQ == 4) sa = (red[tid] + red[MR + tid]) + (red[2 * MR + tid] + red[3 * MR + tid]);
-    else sa = red[tid] + red[MR + tid];
-    a_out[m0 + tid] = sa + b2v;
-  }
+  static_assert(WQ == 4, "four column waves' partial scores");
+  if (tid < MR && m0 + tid < M)
+    a_out[m0 + tid] = ((red[tid] + red[MR + tid]) + (red[2 * MR + tid] + red[3 * MR + tid])) + b2v;
 }
 
 // -----------------------------------------------------------------------------------------
@@ -335,8 +299,7 @@ __global__ __launch_bounds__(512, 1) void head_score2_kernel(const bf16* __restr
 // -----------------------------------------------------------------------------------------
 template <int TPT>
 __global__ __launch_bounds__(384) void head_pool2_kernel(const bf16* __restrict__ table, const int* __restrict__ ids,
-                                                         const float* __restrict__ a, const float* __restrict__ a2,
-                                                         const int* __restrict__ tokens,
+                                                         const float* __restrict__ a, const int* __restrict__ tokens,
                                                          int T, int D, float* __restrict__ pooled,
                                                          float* __restrict__ alpha, const int* __restrict__ nreal,
                                                          bf16* __restrict__ pooled_b) {
@@ -367,7 +330,7 @@ __global__ __launch_bounds__(384) void head_pool2_kernel(const bf16* __restrict_
   for (int c = 0; c < 2; ++c) {
     const int t = lane + 64 * c;
     keep[c] = t < T && (tokens == nullptr || tokens[((size_t)id * 2 + 1) * T + t] != 0);
-    av[c] = keep[c] ? (a2 != nullptr ? a[(size_t)u * T + t] + a2[(size_t)u * T + t] : a[(size_t)u * T + t]) : -INFINITY;
+    av[c] = keep[c] ? a[(size_t)u * T + t] : -INFINITY;
     m = fmaxf(m, av[c]);
   }
   m = wave_max(m);
@@ -509,11 +472,6 @@ constexpr int WSTAGE = E_BYTES + X_BYTES + DA_BYTES;
 constexpr int MAX_SPLIT_TITLES = 1024;  // title ids of one split, staged in LDS up front
 
 // (more opaque LDS accesses, see lds_read128)
-__device__ __forceinline__ s16x4 tr_read(uint32_t addr) {
-  s16x4 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
-  return v;
-}
 __device__ __forceinline__ float lds_read32(uint32_t addr) {
   float v;
   asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(addr));
@@ -527,8 +485,6 @@ __device__ __forceinline__ int lds_read32i(uint32_t addr) {
 __device__ __forceinline__ void lds_write128(uint32_t addr, u32x4_t v) {
   asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
 }
-
-__device__ __forceinline__ int swz(int row) { return ((row & 3) | (((row >> 3) & 1) << 2)) << 1; }
 
 // ids_lds: LDS byte address of the split's title ids (title u at ids_lds + 4 (u - u_lo)): a
 // global load of ids[] here would be an ordinary load whose use makes the compiler wait
@@ -570,41 +526,17 @@ __device__ __forceinline__ void wg_stage(char* base, const bf16* __restrict__ e,
   }
 }
 
-__device__ __forceinline__ uint32_t tr_off_e(int r0, int col0, int q, int p) {  // 256-B rows
-  const int c = (col0 >> 3) + (p >> 1);
-  const int r = r0 + q;
-  return (uint32_t)(r * 256 + ((c ^ swz(r)) << 4) + (p & 1) * 8);
-}
-__device__ __forceinline__ uint32_t tr_off_x(int r0, int col0, int q, int p) {  // 512-B rows
-  const int c = (col0 >> 3) + (p >> 1);
-  const int r = r0 + q;
-  return (uint32_t)(r * 512 + ((c ^ swz(r)) << 4) + (p & 1) * 8);
-}
-
-#define LGKM_TIE8(r)                                                                                  \
-  asm volatile("s_waitcnt lgkmcnt(0)"                                                                 \
-               : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), \
-                 "+v"(r[7]))
-
-__device__ __forceinline__ bf16x8 join(s16x4 a, s16x4 b) {
-  bf16x4 x = __builtin_bit_cast(bf16x4, a), y = __builtin_bit_cast(bf16x4, b);
-  return bf16x8{x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
-}
-
 // stage landed for this wave except `inflight` younger stages (4 glds each), then barrier
 __device__ __forceinline__ void wg_sync(int inflight) {
   __builtin_amdgcn_sched_barrier(0);
-  if (inflight >= 4) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else if (inflight == 3) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else if (inflight == 2) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  if (inflight >= 2) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   else if (inflight == 1) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// rewrite this thread's 16-B chunk of a stage's E tile: e -> g = da (1 - e^2) (bf16); STATS:
+// rewrite this thread's 16-B chunk of a stage's E tile: e -> g = da (1 - e^2) (bf16), and
 // accumulate dw2 += da e and dsum += g (the rounded g the GEMM consumes) for its 8 columns
-template <bool STATS>
 __device__ __forceinline__ void wg_transform(uint32_t base, int tid, int wave, float (&dw2)[8], float (&dsum)[8]) {
   const int r = tid >> 4, pc = tid & 15;
   const uint32_t ea = base + r * 256 + pc * 16;
@@ -617,37 +549,34 @@ __device__ __forceinline__ void wg_transform(uint32_t base, int tid, int wave, f
   for (int k = 0; k < 8; ++k) {
     const float f = (float)ev[k];
     o[k] = f2bf(dav * (1.0f - f * f));
-    if constexpr (STATS) {
-      dw2[k] += dav * f;
-      dsum[k] += (float)o[k];
-    }
+    dw2[k] += dav * f;
+    dsum[k] += (float)o[k];
   }
   lds_write128(ea, __builtin_bit_cast(u32x4_t, o));
 }
 
-// IL (the default): the e -> g rewrite of stage st+1 no longer runs as its own LDS round trip
-// in front of stage st's MFMAs (25 us of the 128 in isolation: the in-LDS-pass form measured 104);
-// its two LDS reads join the fragment reads, one wait covers both, and its VALU work is spread
-// between the MFMA groups (the MFMAs do not depend on it), its write after them.  The column
-// sums dw2 / db1 accumulate in every block (a few FMAs) and only the k-tile-0 blocks store them.
+// The e -> g rewrite of stage st+1 is interleaved with stage st's MFMAs rather than run as its
+// own LDS round trip in front of them: its two LDS reads join the fragment reads and its VALU
+// work is spread between the MFMA groups (the MFMAs do not depend on it), its write after them.
+// Only stage 0 is rewritten on its own (wg_transform, in the prologue).  The column sums dw2 /
+// db1 accumulate in every block (a few FMAs) and only the k-tile-0 blocks store them.
 //
-// SW (staged waits, with IL; the default): the stage's LDS reads go out in the order the MFMA groups consume
-// them -- the transform's e chunk and da first, the 8 X fragment halves, then g fragment i --
-// and each group waits only for its own reads (lgkmcnt 6 / 4 / 2 / 0: LDS reads retire in
-// order), so group 0's MFMAs start while the reads of groups 1-3 are still in the LDS queue
-// (the 8 waves leave one barrier together and all want the LDS at once).
-template <int NSTAGE, bool IL = false, bool SW = false>
+// Staged waits: the stage's LDS reads go out in the order the MFMA groups consume them -- the
+// transform's e chunk and da first, the 8 X fragment halves, then g fragment i -- and each
+// group waits only for its own reads (lgkmcnt 6 / 4 / 2 / 0: LDS reads retire in order), so
+// group 0's MFMAs start while the reads of groups 1-3 are still in the LDS queue (the 8 waves
+// leave one barrier together and all want the LDS at once).
+template <int NSTAGE>
 __global__ __launch_bounds__(512, 1) void head_wgrad_kernel(const bf16* __restrict__ e, const bf16* __restrict__ table,
                                                             const int* __restrict__ ids, const float* __restrict__ da,
                                                             int M, int T, int D, int Q, float* __restrict__ P,
                                                             float* __restrict__ dw2p, float* __restrict__ dsump,
-                                                            int tiles_k, int ntiles, int mchunk, int no_transform,
+                                                            int tiles_k, int ntiles, int mchunk,
                                                             const int* __restrict__ nreal) {
   __shared__ __attribute__((aligned(16))) char smem[NSTAGE * WSTAGE + 4 * MAX_SPLIT_TITLES];
   // XCD-aware order: all tiles of one split (same e / x row panel) on one XCD's L2
-  const int bid = blockIdx.x, nwg = gridDim.x;
-  const int xcd = bid & 7, qq = nwg >> 3, rmd = nwg & 7;
-  const int t = (xcd < rmd ? xcd * (qq + 1) : rmd * (qq + 1) + (xcd - rmd) * qq) + (bid >> 3);
+  const int nwg = gridDim.x;
+  const int t = xcd_block(blockIdx.x, nwg);
   const int s = t / ntiles, tile = t - s * ntiles;
   const int qt = tile / tiles_k, kt = tile - qt * tiles_k;
   const int q0 = qt * WQT, k0 = kt * WKT;
@@ -663,8 +592,7 @@ __global__ __launch_bounds__(512, 1) void head_wgrad_kernel(const bf16* __restri
   const int me = min(M, mb + mchunk);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wn = wave >> 2, wk = wave & 3;
-  const bool stats = kt == 0 && !no_transform;  // block-uniform
-  const bool xform = !no_transform;  // diagnostic A/B: raw e as the dY operand
+  const bool stats = kt == 0;  // block-uniform: the k-tile-0 blocks store the column sums
 
   f32x4 acc[4][4];
 #pragma unroll
@@ -691,21 +619,20 @@ __global__ __launch_bounds__(512, 1) void head_wgrad_kernel(const bf16* __restri
       wg_stage(smem + i * WSTAGE, e, table, ids_lds, u_lo, da, T, D, Q, q0, k0, mb + i * WTM, me, wave, lane);
   if (nsteps > 0) {
     wg_sync(nsteps - 1 < NSTAGE - 2 ? nsteps - 1 : NSTAGE - 2);  // stage 0 landed
-    if (stats || (IL && xform)) wg_transform<true>(lds0, tid, wave, sw2, ssum);
-    else if (xform) wg_transform<false>(lds0, tid, wave, sw2, ssum);
+    wg_transform(lds0, tid, wave, sw2, ssum);
   }
   const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
   const int r0 = g * 8;
   uint32_t xo[4][2], yo[4][2];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    xo[j][0] = E_BYTES + tr_off_x(r0, wk * 64 + j * 16, q, p);
-    xo[j][1] = E_BYTES + tr_off_x(r0 + 4, wk * 64 + j * 16, q, p);
+    xo[j][0] = E_BYTES + tr_off(2 * WKT, r0, wk * 64 + j * 16, q, p);
+    xo[j][1] = E_BYTES + tr_off(2 * WKT, r0 + 4, wk * 64 + j * 16, q, p);
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    yo[i][0] = tr_off_e(r0, wn * 64 + i * 16, q, p);
-    yo[i][1] = tr_off_e(r0 + 4, wn * 64 + i * 16, q, p);
+    yo[i][0] = tr_off(2 * WQT, r0, wn * 64 + i * 16, q, p);
+    yo[i][1] = tr_off(2 * WQT, r0 + 4, wn * 64 + i * 16, q, p);
   }
   for (int st = 0; st < nsteps; ++st) {
     // stage st+1 landed (all waves), stage st fully rewritten (all waves' transform writes,
@@ -715,112 +642,14 @@ __global__ __launch_bounds__(512, 1) void head_wgrad_kernel(const bf16* __restri
     if (st + NSTAGE - 1 < nsteps)
       wg_stage(smem + ((st + NSTAGE - 1) % NSTAGE) * WSTAGE, e, table, ids_lds, u_lo, da, T, D, Q, q0, k0,
                mb + (st + NSTAGE - 1) * WTM, me, wave, lane);
-    if constexpr (IL && SW) {
-      const bool tr = st + 1 < nsteps && xform;  // block-uniform
-      const uint32_t base = lds0 + (st % NSTAGE) * WSTAGE;
-      const uint32_t nb = lds0 + ((st + 1) % NSTAGE) * WSTAGE;
-      const uint32_t ea = nb + (tid >> 4) * 256 + (tid & 15) * 16;
-      // 18 reads whatever tr is (stage st+1's buffer is always a valid LDS address), so the
-      // counted waits are immediates
-      u32x4_t ev4 = lds_read128(ea);
-      float dav = lds_read32(nb + E_BYTES + X_BYTES + wave * 256 + (tid >> 4) * 4);
-      s16x4 xr[8], yr[8];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        xr[2 * j] = tr_read(base + xo[j][0]);
-        xr[2 * j + 1] = tr_read(base + xo[j][1]);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        yr[2 * i] = tr_read(base + yo[i][0]);
-        yr[2 * i + 1] = tr_read(base + yo[i][1]);
-      }
-      asm volatile("s_waitcnt lgkmcnt(6)"
-                   : "+v"(ev4), "+v"(dav), "+v"(xr[0]), "+v"(xr[1]), "+v"(xr[2]), "+v"(xr[3]), "+v"(xr[4]),
-                     "+v"(xr[5]), "+v"(xr[6]), "+v"(xr[7]), "+v"(yr[0]), "+v"(yr[1]));
-      __builtin_amdgcn_sched_barrier(0);
-      const bf16x8 ev = __builtin_bit_cast(bf16x8, ev4);
-      bf16x8 o;
-      bf16x8 xb[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) xb[j] = join(xr[2 * j], xr[2 * j + 1]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if (i == 1) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(yr[2]), "+v"(yr[3]));
-        if (i == 2) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(yr[4]), "+v"(yr[5]));
-        if (i == 3) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(yr[6]), "+v"(yr[7]));
-        const bf16x8 ya = join(yr[2 * i], yr[2 * i + 1]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xb[j], ya, acc[i][j], 0, 0, 0);
-        if (tr) {
-#pragma unroll
-          for (int k = 2 * i; k < 2 * i + 2; ++k) {
-            const float f = (float)ev[k];
-            o[k] = f2bf(dav * (1.0f - f * f));
-            sw2[k] += dav * f;
-            ssum[k] += (float)o[k];
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if (tr) lds_write128(ea, __builtin_bit_cast(u32x4_t, o));
-      __builtin_amdgcn_sched_barrier(0);
-      continue;
-    }
-    if constexpr (IL) {
-      const bool tr = st + 1 < nsteps && xform;  // block-uniform
-      const uint32_t base = lds0 + (st % NSTAGE) * WSTAGE;
-      const uint32_t nb = lds0 + ((st + 1) % NSTAGE) * WSTAGE;
-      const uint32_t ea = nb + (tid >> 4) * 256 + (tid & 15) * 16;
-      s16x4 xr[8], yr[8];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        xr[2 * j] = tr_read(base + xo[j][0]);
-        xr[2 * j + 1] = tr_read(base + xo[j][1]);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        yr[2 * i] = tr_read(base + yo[i][0]);
-        yr[2 * i + 1] = tr_read(base + yo[i][1]);
-      }
-      u32x4_t ev4 = u32x4_t{0u, 0u, 0u, 0u};
-      float dav = 0.f;
-      if (tr) {
-        ev4 = lds_read128(ea);
-        dav = lds_read32(nb + E_BYTES + X_BYTES + wave * 256 + (tid >> 4) * 4);
-      }
-      LGKM_TIE8(xr);
-      LGKM_TIE8(yr);
-      asm volatile("" : "+v"(ev4), "+v"(dav));
-      __builtin_amdgcn_sched_barrier(0);
-      const bf16x8 ev = __builtin_bit_cast(bf16x8, ev4);
-      bf16x8 o;
-      bf16x8 xb[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) xb[j] = join(xr[2 * j], xr[2 * j + 1]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const bf16x8 ya = join(yr[2 * i], yr[2 * i + 1]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xb[j], ya, acc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int k = 2 * i; k < 2 * i + 2; ++k) {  // two of the eight transform elements per MFMA group
-          const float f = (float)ev[k];
-          o[k] = f2bf(dav * (1.0f - f * f));
-          sw2[k] += dav * f;
-          ssum[k] += (float)o[k];
-        }
-      }
-      if (tr) lds_write128(ea, __builtin_bit_cast(u32x4_t, o));
-      __builtin_amdgcn_sched_barrier(0);
-      continue;
-    }
-    if (st + 1 < nsteps) {
-      const uint32_t nb = lds0 + ((st + 1) % NSTAGE) * WSTAGE;
-      if (stats) wg_transform<true>(nb, tid, wave, sw2, ssum);
-      else if (xform) wg_transform<false>(nb, tid, wave, sw2, ssum);
-    }
+    const bool tr = st + 1 < nsteps;  // block-uniform
     const uint32_t base = lds0 + (st % NSTAGE) * WSTAGE;
+    const uint32_t nb = lds0 + ((st + 1) % NSTAGE) * WSTAGE;
+    const uint32_t ea = nb + (tid >> 4) * 256 + (tid & 15) * 16;
+    // 18 reads whatever tr is (stage st+1's buffer is always a valid LDS address), so the
+    // counted waits are immediates
+    u32x4_t ev4 = lds_read128(ea);
+    float dav = lds_read32(nb + E_BYTES + X_BYTES + wave * 256 + (tid >> 4) * 4);
     s16x4 xr[8], yr[8];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -832,20 +661,35 @@ __global__ __launch_bounds__(512, 1) void head_wgrad_kernel(const bf16* __restri
       yr[2 * i] = tr_read(base + yo[i][0]);
       yr[2 * i + 1] = tr_read(base + yo[i][1]);
     }
-    LGKM_TIE8(xr);
-    LGKM_TIE8(yr);
+    asm volatile("s_waitcnt lgkmcnt(6)"
+                 : "+v"(ev4), "+v"(dav), "+v"(xr[0]), "+v"(xr[1]), "+v"(xr[2]), "+v"(xr[3]), "+v"(xr[4]),
+                   "+v"(xr[5]), "+v"(xr[6]), "+v"(xr[7]), "+v"(yr[0]), "+v"(yr[1]));
     __builtin_amdgcn_sched_barrier(0);
+    const bf16x8 ev = __builtin_bit_cast(bf16x8, ev4);
+    bf16x8 o;
     bf16x8 xb[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) xb[j] = join(xr[2 * j], xr[2 * j + 1]);
-    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
+      if (i == 1) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(yr[2]), "+v"(yr[3]));
+      if (i == 2) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(yr[4]), "+v"(yr[5]));
+      if (i == 3) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(yr[6]), "+v"(yr[7]));
       const bf16x8 ya = join(yr[2 * i], yr[2 * i + 1]);
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xb[j], ya, acc[i][j], 0, 0, 0);
+      if (tr) {
+#pragma unroll
+        for (int k = 2 * i; k < 2 * i + 2; ++k) {  // two of the eight transform elements per MFMA group
+          const float f = (float)ev[k];
+          o[k] = f2bf(dav * (1.0f - f * f));
+          sw2[k] += dav * f;
+          ssum[k] += (float)o[k];
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
     }
-    __builtin_amdgcn_s_setprio(0);
+    if (tr) lds_write128(ea, __builtin_bit_cast(u32x4_t, o));
     __builtin_amdgcn_sched_barrier(0);
   }
   // lane holds P[q][k .. k+3]: q = tile column (lane % 16), k = 4 consecutive (lane / 16)
@@ -1131,22 +975,6 @@ constexpr int G_BYTES = WTM * GQT * 2;  // 24 KB
 constexpr int GX_BYTES = WTM * GKT * 2;  // 8 KB
 constexpr int GSTB = G_BYTES + GX_BYTES;  // 32 KB
 
-__device__ __forceinline__ uint32_t tr_off_pitch(int pitch, int r0, int col0, int q, int p) {
-  const int c = (col0 >> 3) + (p >> 1);
-  const int r = r0 + q;
-  return (uint32_t)(r * pitch + ((c ^ swz(r)) << 4) + (p & 1) * 8);
-}
-
-// a fragment = two ds_read_b64_tr_b16 four rows apart: the second at an immediate offset.
-// `a` is early-clobber: the first read's destination must not be the address register the
-// second read still needs (the return can land before a queued second read issues).
-template <int OFF>
-__device__ __forceinline__ void tr_read2(uint32_t addr, s16x4& a, s16x4& b) {
-  asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %2 offset:%3"
-               : "=&v"(a), "=v"(b)
-               : "v"(addr), "n"(OFF));
-}
-
 template <int N>
 __device__ __forceinline__ void lgkm_tie4(s16x4 (&r)[4]) {
   asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]) : "n"(N));
@@ -1161,9 +989,8 @@ __global__ __launch_bounds__(512, 1) void head_wgrad_g_kernel(const bf16* __rest
   __shared__ __attribute__((aligned(16))) char smem[NSTAGE * GSTB + 4 * MAX_SPLIT_TITLES];
   constexpr int Q = GQT, QF = 6;
   // XCD-aware order: the k-tiles of one split (same G / X row panel) on one XCD's L2
-  const int bid = blockIdx.x, nwg = gridDim.x;
-  const int xcd = bid & 7, qq = nwg >> 3, rmd = nwg & 7;
-  const int t = (xcd < rmd ? xcd * (qq + 1) : rmd * (qq + 1) + (xcd - rmd) * qq) + (bid >> 3);
+  const int nwg = gridDim.x;
+  const int t = xcd_block(blockIdx.x, nwg);
   const int s = t / tiles_k, kt = t - s * tiles_k;
   const int k0 = kt * GKT;
   int Ur = U;
@@ -1247,9 +1074,9 @@ __global__ __launch_bounds__(512, 1) void head_wgrad_g_kernel(const bf16* __rest
   const int r0 = g * 8;
   uint32_t xo[4], yo[QF];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) xo[j] = G_BYTES + tr_off_pitch(2 * GKT, r0, wk * 64 + j * 16, q, p);
+  for (int j = 0; j < 4; ++j) xo[j] = G_BYTES + tr_off(2 * GKT, r0, wk * 64 + j * 16, q, p);
 #pragma unroll
-  for (int i = 0; i < QF; ++i) yo[i] = tr_off_pitch(2 * GQT, r0, wq * QF * 16 + i * 16, q, p);
+  for (int i = 0; i < QF; ++i) yo[i] = tr_off(2 * GQT, r0, wq * QF * 16 + i * 16, q, p);
   for (int st = 0; st < nsteps; ++st) {
     // stage st landed (this wave's 4 glds, then every wave's); every wave is done with st - 1
     const int left = nsteps - 1 - st;
@@ -1328,7 +1155,6 @@ __global__ __launch_bounds__(512, 1) void head_wgrad_g_kernel(const bf16* __rest
   }
 }
 
-int g_cus = 0;
 int g_score_ilv = 1;  // head_score2: next stage's pieces interleaved with the MFMA rows
 int g_score_rows = 0;  // head_score2 row tile: 0 = by the rounds rule, 160 / 192 forced (benchmarks)
 
@@ -1349,74 +1175,49 @@ extern "C" int fr_head_score(const void* table, const int* ids, int U, int T, in
   if (!fr_head_supported(D, Q, T)) return 1;
   const int M = U * T;
   if (M == 0) return 0;
-  // Q = 384 (the DistilBERT head): 192-row tiles, BK 64, 2 stages, staged LDS waits (steady step
-  // 0.5452-0.5473 vs 0.5477-0.5520 ms for one wait, profiles/r3_ab_score_sw.txt; the X-only
-  // LDS ring with W1 fragments from L2 ran 100 vs 75 us, profiles/r4_ab_head_score3.txt)
-  // Row tile: one block per CU, so the grid runs in ceil(blocks / CUs) rounds, each as long as
-  // its block's stages ((rows + 384) x 128 B per k-tile): 160-row tiles when that gives fewer
-  // stage bytes over the rounds than 192 (M = 80,000 on 256 CUs: 500 blocks in 2 rounds of 544
-  // vs 417 in 2 rounds of 576)
+#define LAUNCH_S2(QF_, RF_, IL_)                                                                                    \
+  hipLaunchKernelGGL((head_score2_kernel<QF_, RF_, IL_>), dim3((M + 32 * RF_ - 1) / (32 * RF_)), dim3(512), 0, s,   \
+                     (const bf16*)table, ids, M, T, D, (const bf16*)W1, b1, w2, b2, (bf16*)e_out, a_out, nreal)
+  // Q = 384 (the DistilBERT head).  Row tile: one block per CU, so the grid runs in
+  // ceil(blocks / CUs) rounds, each as long as its block's stages ((rows + 384) x 128 B per
+  // k-tile): 160-row tiles when that gives fewer stage bytes over the rounds than 192
+  // (M = 80,000 on 256 CUs: 500 blocks in 2 rounds of 544 vs 417 in 2 rounds of 576)
   if (Q == 384) {
-    if (g_cus == 0) {
-      int dev = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&g_cus, hipDeviceAttributeMultiprocessorCount, dev);
-      if (g_cus <= 0) g_cus = 256;
-    }
+    const int cus = fr_num_cus();
     // a padded step graph (nreal given): blocks past the real titles exit at once, and the real
     // count is the padded one less up to a bucket (128 titles) -- judge the rounds at mid-bucket
     const long Me = nreal != nullptr ? std::max<long>((long)M - 64L * T, (long)T) : (long)M;
-    const long rounds192 = ((Me + 191) / 192 + g_cus - 1) / g_cus, rounds160 = ((Me + 159) / 160 + g_cus - 1) / g_cus;
+    const long rounds192 = ((Me + 191) / 192 + cus - 1) / cus, rounds160 = ((Me + 159) / 160 + cus - 1) / cus;
     const bool r160 = g_score_rows == 160 || (g_score_rows == 0 && rounds160 * (160 + 384) < rounds192 * (192 + 384));
-#define LAUNCH_S2(RF_, IL_)                                                                                  \
-  hipLaunchKernelGGL((head_score2_kernel<6, RF_, 64, 2, 4, true, IL_>), dim3((M + 32 * RF_ - 1) / (32 * RF_)),     \
-                     dim3(512), 0, s, (const bf16*)table, ids, M, T, D, (const bf16*)W1, b1, w2, b2, (bf16*)e_out, \
-                     a_out, Q, nreal)
     if (r160) {
-      if (g_score_ilv) LAUNCH_S2(5, true);
-      else LAUNCH_S2(5, false);
+      if (g_score_ilv) LAUNCH_S2(6, 5, true);
+      else LAUNCH_S2(6, 5, false);
     } else {
-      if (g_score_ilv) LAUNCH_S2(6, true);
-      else LAUNCH_S2(6, false);
+      if (g_score_ilv) LAUNCH_S2(6, 6, true);
+      else LAUNCH_S2(6, 6, false);
     }
-#undef LAUNCH_S2
     return 0;
   }
-  // Q = 128 / 256 (the tiny test backbones): 128-row tiles, the same pipeline
-  if (Q == 256)
-    hipLaunchKernelGGL((head_score2_kernel<4, 4, 64, 2, 4, true>), dim3((M + 127) / 128), dim3(512), 0, s,
-                       (const bf16*)table, ids, M, T, D, (const bf16*)W1, b1, w2, b2, (bf16*)e_out, a_out, Q, nreal);
-  else
-    hipLaunchKernelGGL((head_score2_kernel<2, 4, 64, 2, 4, true>), dim3((M + 127) / 128), dim3(512), 0, s,
-                       (const bf16*)table, ids, M, T, D, (const bf16*)W1, b1, w2, b2, (bf16*)e_out, a_out, Q, nreal);
+  // Q = 128 / 256 (the tiny test backbones): 128-row tiles, the same pipeline, pieces not interleaved
+  if (Q == 256) LAUNCH_S2(4, 4, false);
+  else LAUNCH_S2(2, 4, false);
+#undef LAUNCH_S2
   return 0;
 }
 
-// score partials per row: head_score writes a[slices][M] (the pool sums the slices); every
-// current tiling writes whole scores
-extern "C" int fr_head_score_slices(int Q) {
-  (void)Q;
-  return 1;
-}
-
-extern "C" int fr_head_pool(const void* table, const int* ids, const float* a, int slices, const int* tokens, int U,
-                            int T, int D, float* pooled, float* alpha, const int* nreal, hipStream_t s,
-                            void* pooled_b) {
-  const float* a2 = slices == 2 ? a + (size_t)U * T : nullptr;
+extern "C" int fr_head_pool(const void* table, const int* ids, const float* a, const int* tokens, int U, int T, int D,
+                            float* pooled, float* alpha, const int* nreal, hipStream_t s, void* pooled_b) {
   if (T > MAXT || D % 8 != 0 || D / 8 > 384) return 1;
   if (U == 0) return 0;
   const int TG = 384 / (D / 8), tpt = (T + TG - 1) / TG;
   if (tpt > 32) return 1;  // (fr_head_supported excludes these shapes)
-  {
-#define LAUNCH_POOL2(N)                                                                                          \
-  hipLaunchKernelGGL(head_pool2_kernel<N>, dim3(U), dim3(384), 0, s, (const bf16*)table, ids, a, a2, tokens, T, D, \
+#define LAUNCH_POOL2(N)                                                                                        \
+  hipLaunchKernelGGL(head_pool2_kernel<N>, dim3(U), dim3(384), 0, s, (const bf16*)table, ids, a, tokens, T, D, \
                      pooled, alpha, nreal, (bf16*)pooled_b)
-    if (tpt <= 13) LAUNCH_POOL2(13);
-    else if (tpt <= 16) LAUNCH_POOL2(16);
-    else LAUNCH_POOL2(32);
+  if (tpt <= 13) LAUNCH_POOL2(13);
+  else if (tpt <= 16) LAUNCH_POOL2(16);
+  else LAUNCH_POOL2(32);
 #undef LAUNCH_POOL2
-    return 0;
-  }
   return 0;
 }
 
@@ -1425,16 +1226,13 @@ extern "C" int fr_head_pool_bwd(const void* table, const int* ids, const float* 
   if (T > MAXT || D % 8 != 0 || D / 8 > 128) return 1;
   if (U == 0) return 0;
   const int tpw = (T + 5) / 6;  // <= 22 at T <= MAXT
-  {
 #define LAUNCH_PBWD2(N)                                                                                           \
   hipLaunchKernelGGL(head_pool_bwd2_kernel<N>, dim3(U), dim3(384), 0, s, (const bf16*)table, ids, alpha, g, T, D, \
                      da, db2p, nreal)
-    if (tpw <= 9) LAUNCH_PBWD2(9);
-    else if (tpw <= 11) LAUNCH_PBWD2(11);
-    else LAUNCH_PBWD2(22);
+  if (tpw <= 9) LAUNCH_PBWD2(9);
+  else if (tpw <= 11) LAUNCH_PBWD2(11);
+  else LAUNCH_PBWD2(22);
 #undef LAUNCH_PBWD2
-    return 0;
-  }
   return 0;
 }
 
@@ -1444,12 +1242,6 @@ extern "C" long fr_head_wgrad(const void* e, const void* table, const int* ids, 
                               float* db2, float* scratch, const int* nreal, hipStream_t s) {
   if (!fr_head_supported(D, Q, T)) return -1;
   const int M = U * T;
-  if (g_cus == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&g_cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (g_cus <= 0) g_cus = 256;
-  }
   const int tiles_k = D / WKT, ntiles = (Q / WQT) * tiles_k;
   // one wave of blocks (one per CU), each split >= 8 stages of 32 rows.  The first form left
   // 16 CUs out for the lookahead stream's sampler / dedup, which then still ran beside this
@@ -1457,13 +1249,13 @@ extern "C" long fr_head_wgrad(const void* e, const void* table, const int* ids, 
   // The register-bitonic dedup (30 us) finishes before this kernel starts, so every CU gets a
   // block: 28 splits vs 26 measured 0.5709 / 0.5707 vs 0.5780 / 0.5791 ms per step (A/B/A/B,
   // profiles/r3_ab_wgrad_splits.txt)
-  int S = g_cus / ntiles;
+  int S = fr_num_cus() / ntiles;
   const int smax = (M + 8 * WTM - 1) / (8 * WTM);
   S = S < 1 ? 1 : (S > smax ? smax : S);
   if (S < 1) S = 1;
   int mchunk = ((M + S - 1) / S + WTM - 1) / WTM * WTM;
   if (mchunk < WTM) mchunk = WTM;
-  // a split's title ids (32-row forms) / cache-row table (64-row form) must fit in LDS
+  // a split's title ids must fit in LDS
   const int cap = (MAX_SPLIT_TITLES - 2) * T / WTM * WTM;
   if (mchunk > cap) mchunk = cap < 64 ? 64 : cap / 64 * 64;
   S = (M + mchunk - 1) / mchunk;
@@ -1473,12 +1265,10 @@ extern "C" long fr_head_wgrad(const void* e, const void* table, const int* ids, 
   float* P = scratch;
   float* dw2p = scratch + (long)S * Q * D;
   float* dsump = dw2p + (long)S * Q;
-  // 32-row stages x4 with staged LDS waits: 139 us at U = 1600 vs 146 / 149 for x5 / x6 and
-  // 183 for a 64-row form (benchmarks/head_bench.py); staged waits: steady step 0.5498-0.5529
-  // vs 0.5509-0.5534 ms over two calls (profiles/r3_ab_wgrad_sw_bump.txt)
+  // four 32-row stages: 139 us at U = 1600 vs 146 / 149 for x5 / x6 (benchmarks/head_bench.py)
   if (M > 0) {
-    hipLaunchKernelGGL((head_wgrad_kernel<4, true, true>), dim3(S * ntiles), dim3(512), 0, s, (const bf16*)e,
-                       (const bf16*)table, ids, da, M, T, D, Q, P, dw2p, dsump, tiles_k, ntiles, mchunk, 0, nreal);
+    hipLaunchKernelGGL((head_wgrad_kernel<4>), dim3(S * ntiles), dim3(512), 0, s, (const bf16*)e,
+                       (const bf16*)table, ids, da, M, T, D, Q, P, dw2p, dsump, tiles_k, ntiles, mchunk, nreal);
   } else {
     (void)hipMemsetAsync(scratch, 0, need * sizeof(float), s);
   }
@@ -1513,8 +1303,6 @@ extern "C" int fr_head_pool_bwd_g(const void* table, const int* ids, const float
   return 0;
 }
 
-extern "C" void fr_head_wgrad_g_set_kt(int kt) { (void)kt; }  // one form left (the benchmarks' knob)
-
 // scratch = null: returns the fp32 scratch element count needed; else launches.  G = the g rows
 // (the e buffer after the rewrite), cs its column partials.
 extern "C" long fr_head_wgrad_g(const void* G, const void* table, const int* ids, const float* cs, const float* db2p,
@@ -1524,16 +1312,9 @@ extern "C" long fr_head_wgrad_g(const void* G, const void* table, const int* ids
   // pend (optional): a deferred small-GEMM split-K reduction (fr_small_gemm_take_pending), run
   // in pend_total extra blocks of the reduce launch
   if (!fr_head_g_supported(D, Q, T)) return -1;
-  if (g_cus == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&g_cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (g_cus <= 0) g_cus = 256;
-  }
-  const int KT = GKT;
-  const int tiles_k = D / KT;
+  const int tiles_k = D / GKT;
   // one block per CU: S splits of whole titles
-  int S = g_cus / tiles_k;
+  int S = fr_num_cus() / tiles_k;
   if (S < 1) S = 1;
   int tps = (U + S - 1) / S;
   if (tps < 1) tps = 1;

@@ -651,7 +651,6 @@ __global__ __launch_bounds__(256, 1) void title_attn_packed_kernel(const bf16* _
 }
 
 int g_ta_waves = -2;  // default: persistent, 2-deep prefetch, 1 wave per SIMD (kernel_bench.py)
-int g_ta_cus = 0;
 
 }  // namespace
 
@@ -665,13 +664,7 @@ extern "C" int fr_title_attention_bf16(const void* qkv, const int* mask, void* o
   if (pairs == 0) return 0;
   const int w = g_ta_waves;
   if (w <= 0) {  // persistent, prefetching: w = 0 -> 2 waves/SIMD (spills a little), w = -1 -> 1 wave/SIMD
-    if (g_ta_cus == 0) {
-      int dev = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&g_ta_cus, hipDeviceAttributeMultiprocessorCount, dev);
-      if (g_ta_cus <= 0) g_ta_cus = 256;
-    }
-    int blocks = g_ta_cus * (w == 0 ? 2 : 1);
+    int blocks = fr_num_cus() * (w == 0 ? 2 : 1);
     const int need = (pairs + 3) / 4;
     blocks = blocks < need ? blocks : need;
     if (w == -2)
@@ -703,14 +696,8 @@ extern "C" int fr_title_attention_drop_bf16(const void* qkv, const int* mask, vo
   const int pairs = n_titles * H;
   if (pairs == 0) return 0;
   if (g_ta_waves == -2) {  // persistent 2-deep prefetching form (default), as the eval forward
-    if (g_ta_cus == 0) {
-      int dev = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&g_ta_cus, hipDeviceAttributeMultiprocessorCount, dev);
-      if (g_ta_cus <= 0) g_ta_cus = 256;
-    }
     const int need = (pairs + 3) / 4;
-    const int blocks = g_ta_cus < need ? g_ta_cus : need;
+    const int blocks = fr_num_cus() < need ? fr_num_cus() : need;
     hipLaunchKernelGGL((title_attn_pkernel<1, 2, true>), dim3(blocks), dim3(256), 0, s, (const bf16*)qkv, mask,
                        (bf16*)out, pairs, T, H, D, pdrop, seed, offset);
     return 0;
@@ -738,13 +725,7 @@ extern "C" int fr_title_attention_packed_bf16(const void* qkv, const int* rowmap
   if (T < 1 || T > 64 || D != H * DH) return 1;
   const int pairs = n_titles * H;
   if (pairs == 0) return 0;
-  if (g_ta_cus == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&g_ta_cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (g_ta_cus <= 0) g_ta_cus = 256;
-  }
-  int blocks = g_ta_cus;
+  int blocks = fr_num_cus();
   const int need = (pairs + 3) / 4;
   blocks = blocks < need ? blocks : need;
   hipLaunchKernelGGL(title_attn_packed_kernel, dim3(blocks), dim3(256), 0, s, (const bf16*)qkv, rowmap, kv_start, kv_len,

@@ -549,18 +549,7 @@ __global__ __launch_bounds__(256, 1) void title_attn_bwd_pkernel(const bf16* __r
 }
 
 int g_tab_variant = 1;  // 1: persistent prefetching (default), 0: one-shot
-int g_tab_cus = 0;
 int g_tab_drop_split = 1;  // dropout backward: split prefetch (the variant setter's 10: one block)
-
-int tab_cus() {
-  if (g_tab_cus == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&g_tab_cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (g_tab_cus <= 0) g_tab_cus = 256;
-  }
-  return g_tab_cus;
-}
 
 }  // namespace
 
@@ -576,7 +565,7 @@ extern "C" int fr_title_attention_bwd_bf16(const void* qkv, const void* dout, co
   const int pairs = n_titles * H;
   if (pairs == 0) return 0;
   if (g_tab_variant == 1) {
-    int blocks = tab_cus();
+    int blocks = fr_num_cus();
     const int need = (pairs + 3) / 4;
     blocks = blocks < need ? blocks : need;
     hipLaunchKernelGGL(title_attn_bwd_pkernel<false>, dim3(blocks), dim3(256), 0, s, (const bf16*)qkv, (const bf16*)dout,
@@ -596,7 +585,7 @@ extern "C" int fr_title_attention_bwd_drop_bf16(const void* qkv, const void* dou
   if (pairs == 0) return 0;
   if (g_tab_variant == 1) {
     const int need = (pairs + 3) / 4;
-    const int blocks = tab_cus() < need ? tab_cus() : need;
+    const int blocks = fr_num_cus() < need ? fr_num_cus() : need;
     if (g_tab_drop_split)
       hipLaunchKernelGGL((title_attn_bwd_pkernel<true, true>), dim3(blocks), dim3(256), 0, s, (const bf16*)qkv,
                          (const bf16*)dout, mask, (bf16*)dqkv, pairs, T, H, D, pdrop, seed, offset);

@@ -35,7 +35,7 @@ def _golden():
 
 def test_op_set_matches_fixture():
     got, want = set(_registered()), set(_golden())
-    assert len(want) == 81
+    assert len(want) == 80
     assert got == want, f"missing: {sorted(want - got)}; unexpected: {sorted(got - want)}"
 
 

@@ -97,7 +97,7 @@ def test_fused_head_forward_only_skips_e(dev):
     e2, a2 = lib.head_score(table, None, T, w1, b1, w2, b2, True)
     assert e.numel() == 0 and e2.shape == (U * T, Q)
     assert torch.equal(a, a2)
-    a2 = a2.reshape(-1, U * T).sum(0)  # [slices, U*T] partial scores of a Q-sliced tiling
+    a2 = a2.reshape(-1, U * T).sum(0)
     # the score is the row-dot of the fp32 tanh values: agrees with the stored bf16 e to its rounding
     assert _rel(a2 - b2, e2.float() @ w2) < 1e-2
 
