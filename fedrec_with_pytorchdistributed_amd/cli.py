@@ -118,21 +118,16 @@ def main_star(argv: Optional[List[str]] = None) -> int:
     return main_client([pos[1], pos[2], "1", "0", "star", *extra])
 
 
-def main_recommend(argv: Optional[List[str]] = None):
-    """``recommend SNAPSHOT --data_dir=... --k=10 [--limit=N] [--out=recs.jsonl] [--key=value ...]``:
-    rank the whole catalog for every validation impression of the shard (single process, no
-    process group).  ``SNAPSHOT``: a snapshot of ``train/checkpoint.py``, or ``none`` for the freshly
-    initialised model.  Writes one JSON line per impression (``uid``, ``news``: the nid strings best
-    first, ``scores``) to ``--out`` (default: stdout); prints and returns the hr / ndcg / mrr metrics
-    as the final JSON line."""
-    import json
+def _offline_engine(argv: List[str], own: dict, usage: str):
+    """The single-process commands' setup (no process group): ``SNAPSHOT`` (a snapshot of
+    ``train/checkpoint.py``, or ``none`` for the freshly initialised model) and ``--key=value``
+    arguments -- the command's ``own`` keys are filled in place, the rest override the config ->
+    ``(engine, shard)``."""
     import types
 
-    argv = sys.argv[1:] if argv is None else argv
     pos = [a for a in argv if not a.startswith("--")]
     if len(pos) != 1:
-        raise SystemExit("usage: recommend <snapshot|none> --data_dir=... [--k=10] [--limit=N] [--out=FILE] [--k=v]")
-    own = {"k": "10", "limit": "", "out": "", "batch": "256"}
+        raise SystemExit(usage)
     rest = []
     for a in argv:
         if a.startswith("--"):
@@ -155,17 +150,36 @@ def main_recommend(argv: Optional[List[str]] = None):
     model = build_model(cfg, dev)
     if pos[0].lower() != "none":
         ckpt.load_snapshot(pos[0], model, rng=False)
-    eng = LocalEngine(cfg, model, shard, dev)
+    return LocalEngine(cfg, model, shard, dev), shard
+
+
+def _uid_name(shard, i: int) -> str:
+    uids = getattr(shard, "_uids", None) or []
+    u = int(shard.valid.uid[i])
+    return uids[u] if u < len(uids) else f"U{u}"
+
+
+def main_recommend(argv: Optional[List[str]] = None):
+    """``recommend SNAPSHOT --data_dir=... --k=10 [--limit=N] [--out=recs.jsonl] [--key=value ...]``:
+    rank the whole catalog for every validation impression of the shard (single process, no
+    process group).  ``SNAPSHOT``: a snapshot of ``train/checkpoint.py``, or ``none`` for the freshly
+    initialised model.  Writes one JSON line per impression (``uid``, ``news``: the nid strings best
+    first, ``scores``) to ``--out`` (default: stdout); prints and returns the hr / ndcg / mrr metrics
+    as the final JSON line."""
+    import json
+
+    argv = sys.argv[1:] if argv is None else argv
+    own = {"k": "10", "limit": "", "out": "", "batch": "256"}
+    eng, shard = _offline_engine(
+        argv, own, "usage: recommend <snapshot|none> --data_dir=... [--k=10] [--limit=N] [--out=FILE] [--k=v]")
     limit = int(own["limit"]) if own["limit"] else None
     metrics, ids, scores = eng.recommend_valid(int(own["k"]), int(own["batch"]), limit, return_lists=True)
     i2n = shard.index2nid
-    uids = getattr(shard, "_uids", None) or []
     f = open(own["out"], "w") if own["out"] else sys.stdout
     try:
         for i in range(ids.shape[0]):
-            u = int(shard.valid.uid[i])
             keep = ids[i] >= 0
-            f.write(json.dumps({"uid": uids[u] if u < len(uids) else f"U{u}",
+            f.write(json.dumps({"uid": _uid_name(shard, i),
                                 "news": [i2n[int(x)] for x in ids[i][keep]],
                                 "scores": [float(x) for x in scores[i][keep]]}) + "\n")
     finally:
@@ -175,8 +189,35 @@ def main_recommend(argv: Optional[List[str]] = None):
     return metrics
 
 
+def main_evaluate(argv: Optional[List[str]] = None):
+    """``evaluate SNAPSHOT --data_dir=... [--limit=N] [--batch=256] [--out=FILE] [--key=value ...]``:
+    full-impression evaluation of the shard's validation split (single process, no process group):
+    every impression's positive ranked against ALL the negatives it showed
+    (``LocalEngine.validate_full``).  ``SNAPSHOT`` as for ``recommend``.  With ``--out``, one JSON
+    line per impression: ``uid``, ``pos`` (the positive's nid), ``rank`` (ties against the positive;
+    null where a score is NaN) and ``candidates`` (negatives + 1).  Prints and returns the
+    ``full_*`` metrics as the final stdout line."""
+    import json
+
+    argv = sys.argv[1:] if argv is None else argv
+    own = {"limit": "", "out": "", "batch": "256"}
+    eng, shard = _offline_engine(
+        argv, own, "usage: evaluate <snapshot|none> --data_dir=... [--limit=N] [--batch=256] [--out=FILE] [--k=v]")
+    limit = int(own["limit"]) if own["limit"] else None
+    metrics, counts = eng.validate_full(int(own["batch"]), limit, return_counts=True)
+    if own["out"]:
+        i2n = shard.index2nid
+        with open(own["out"], "w") as f:
+            for i in range(counts.shape[0]):
+                gt, eq, nn, nan = (int(x) for x in counts[i])
+                f.write(json.dumps({"uid": _uid_name(shard, i), "pos": i2n[int(shard.valid.pos[i])],
+                                    "rank": None if nan else 1 + gt + eq, "candidates": nn + 1}) + "\n")
+    print(json.dumps(metrics), flush=True)
+    return metrics
+
+
 COMMANDS = {"client": main_client, "server": main_server, "grad_avg": main_grad_avg, "param_avg": main_param_avg,
-            "star": main_star, "recommend": main_recommend}
+            "star": main_star, "recommend": main_recommend, "evaluate": main_evaluate}
 
 
 def main(argv=None) -> int:

@@ -198,6 +198,9 @@ class FedRecConfig:
     # reference round interchange files (client.py:288 model.pt, server.py:27
     # received_model_{k}.pt), written beside snapshot_path; off by default (270 MB each)
     round_artifacts: bool = False
+    # also rank each validation impression's positive against ALL of its negatives after every
+    # validation pass (LocalEngine.validate_full): adds the full_* keys to the round record
+    valid_full: bool = False
     metrics_path: str = ""  # JSONL; empty = metrics.jsonl beside the snapshot on rank 0
     run_name: str = "fedrec"
     wandb_project: str = "Node4"  # only used when FEDREC_WANDB=1 and wandb is importable

@@ -182,6 +182,12 @@ int fr_topk_splits(long B, long N);
 int fr_topk_scores(const float* user, const float* table, const int* exclude, void* ws, float* scores, int* ids, long B,
                    long N, int D, long E, int k, int min_id, hipStream_t s);
 
+// ---- rank_impressions.hip --------------------------------------------------------------------
+long fr_rank_impressions_ws(long M);
+int fr_rank_impressions(const float* user, const float* table, const int* pos, const long long* neg_ptr,
+                        const int* negs, void* ws, int* counts, long B, long N, int D, long I, long M, long row0,
+                        hipStream_t s);
+
 // ---- secagg.hip ------------------------------------------------------------------------------
 int fr_secagg_mask(const float* x, int* out, long n, float scale, float clipv, const unsigned long long* seeds,
                    const int* signs, int npeers, unsigned long long round, hipStream_t s);

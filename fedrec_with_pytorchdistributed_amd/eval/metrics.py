@@ -120,6 +120,41 @@ def metric_sums(scores: np.ndarray) -> np.ndarray:
     return np.array([m["auc"] * n, m["mrr"] * n, m["ndcg5"] * n, m["ndcg10"] * n, n], dtype=np.float64)
 
 
+def impression_sums(counts: np.ndarray) -> np.ndarray:
+    """``[auc, mrr, ndcg5, ndcg10, candidates, n, n_skipped]`` summed over the impressions of
+    ``counts [I, 4]`` that :func:`impression_metrics` keeps (its definitions; the form that can be
+    all-reduced across clients)."""
+    c = np.asarray(counts, dtype=np.int64).reshape(-1, 4)
+    keep = (c[:, 2] > 0) & (c[:, 3] == 0)
+    gt, eq, nn = (c[keep, j].astype(np.float64) for j in range(3))
+    rank = 1.0 + gt + eq
+    auc = ((nn - gt - eq) + 0.5 * eq) / nn
+    inv = 1.0 / np.log2(rank + 1.0)
+    return np.array([auc.sum(), (1.0 / rank).sum(), np.where(rank <= 5, inv, 0.0).sum(),
+                     np.where(rank <= 10, inv, 0.0).sum(), nn.sum() + keep.sum(), float(keep.sum()),
+                     float((~keep).sum())], dtype=np.float64)
+
+
+def impression_means(sums: np.ndarray) -> Dict[str, float]:
+    """:func:`impression_sums` (of one client, or summed over clients) -> the corpus means."""
+    n = int(sums[5])
+    d = float(n) if n else float("nan")
+    return {"auc": float(sums[0] / d), "mrr": float(sums[1] / d), "ndcg5": float(sums[2] / d),
+            "ndcg10": float(sums[3] / d), "mean_candidates": float(sums[4] / d), "n": n, "n_skipped": int(sums[6])}
+
+
+def impression_metrics(counts: np.ndarray) -> Dict[str, float]:
+    """Full-impression ranking quality from ``counts [I, 4]`` = ``(n_gt, n_eq, n_neg, n_nan)`` per
+    impression (``ops.rank_impressions``): the single positive ranked against EVERY negative the
+    impression showed -- the protocol MIND numbers are quoted in -- with the definitions of
+    :func:`batch_metrics`: ``rank = 1 + n_gt + n_eq``, ``auc = ((n_neg - n_gt - n_eq) + n_eq / 2) /
+    n_neg``, ``mrr = 1 / rank``, ``ndcg@k = 1 / log2(rank + 1)`` if ``rank <= k`` else 0.  Impressions
+    without a negative (AUC undefined) or with a NaN score are left out of every mean and counted in
+    ``n_skipped``.  -> corpus means ``auc`` / ``mrr`` / ``ndcg5`` / ``ndcg10``, ``mean_candidates``
+    (positive included), ``n`` and ``n_skipped``; the means are NaN when ``n == 0``."""
+    return impression_means(impression_sums(counts))
+
+
 def topk_metrics(ids: np.ndarray, pos: np.ndarray) -> Dict[str, float]:
     """Full-catalog ranking quality of ordered top-k lists ``ids [I, k]`` (-1 = empty slot) against
     one held-out positive ``pos [I]`` per impression: ``hr@k`` (the positive is in the list),

@@ -25,6 +25,9 @@ adam_flat             model.py:89,93 (K20)         adam.hip: one pass over the f
 dedup / sample_batch  dataset.py:69-86 (K18)       batch.hip: on-device sampling + unique
 topk_scores           (beyond the reference)       topk_scores.hip: fp32 MFMA U V^T fused with an
                                                    ordered per-user top-k (no [B, N] matrix)
+rank_impressions      (beyond the reference)       rank_impressions.hip: an impression's whole
+                                                   negative list gathered, scored and compared
+                                                   with its positive; 4 integers per impression
 ====================  ===========================  ===========================================
 """
 from __future__ import annotations
@@ -235,6 +238,22 @@ def topk_scores(user, table, k: int, exclude=None, min_id: int = 0):
         ex = None if exclude is None else exclude.to(torch.int32).contiguous()
         return tuple(native.require_for(user).topk_scores(user, table, int(k), ex, int(min_id)))
     return ref.topk_scores(user, table, int(k), exclude, int(min_id))
+
+
+def rank_impressions(user, table, pos, neg_ptr, negs, row0: int = 0):
+    """Full-impression ranking -> ``counts [B, 4]`` int32 ``(n_gt, n_eq, n_neg, n_nan)``.  User ``b``
+    (``user [B, D]`` fp32) is impression ``row0 + b`` of the corpus CSR ``pos [I]`` int32, ``neg_ptr
+    [I + 1]`` int64, ``negs [M]`` int32 (the :class:`DeviceSampler`'s arrays, passed whole): ``n_gt``
+    / ``n_eq`` count its negatives whose raw dot product with ``table [N, D]`` fp32 is greater than
+    / equal to the positive's, ``n_neg`` is the list length, ``n_nan`` the candidates (positive
+    included) with a NaN score.  The device kernel writes no score and no gathered row, sums every
+    candidate in one fixed order (a negative with the positive's id ties bitwise) and is bitwise
+    independent of ``B``, ``row0`` and its grid (csrc/rank_impressions.hip); ids are trusted to lie
+    in ``[0, N)``.  :func:`eval.metrics.impression_metrics` turns the counts into AUC / MRR / nDCG."""
+    if _dev(user):
+        native.require_for(user)
+        return torch.ops.fedrec_eval.rank_impressions(user, table, pos, neg_ptr, negs, int(row0))
+    return ref.rank_impressions(user, table, pos, neg_ptr, negs, int(row0))
 
 
 def segment_sum_rows(rows, inv, num_out: int, clip: float = 0.0, noise_std: float = 0.0,

@@ -364,3 +364,34 @@ def topk_scores(user: torch.Tensor, table: torch.Tensor, k: int, exclude: Option
         scores[s:s + c, :kk] = torch.where(ok, sc.gather(1, top), torch.full_like(sc[:, :kk], float("-inf")))
         ids[s:s + c, :kk] = torch.where(ok, top, torch.full_like(top, -1)).to(torch.int32)
     return scores, ids
+
+
+# ---------------------------------------------------------------------------------------
+# Full-impression ranking (oracle of csrc/rank_impressions.hip)
+# ---------------------------------------------------------------------------------------
+def rank_impressions(user: torch.Tensor, table: torch.Tensor, pos: torch.Tensor, neg_ptr: torch.Tensor,
+                     negs: torch.Tensor, row0: int = 0, chunk: int = 1 << 16) -> torch.Tensor:
+    """User ``b`` is impression ``row0 + b`` of the corpus CSR (``pos [I]``, ``neg_ptr [I + 1]``,
+    ``negs [M]``) -> ``counts [B, 4]`` int32 ``(n_gt, n_eq, n_neg, n_nan)``: the negatives whose score
+    ``user[b] . table[n]`` (in the dtype given) is greater than / equal to the positive's, the list
+    length, and the candidates -- positive included -- whose score is NaN (NaN compares false: in
+    neither count).  Every score, the positive's too, is the same row-wise ``(u * v).sum(-1)``, so a
+    negative with the positive's id ties bitwise.  At most ``chunk`` gathered rows exist at a time."""
+    B, row0 = user.shape[0], int(row0)
+    I = pos.numel()
+    if neg_ptr.numel() != I + 1 or row0 < 0 or row0 + B > I:
+        raise ValueError(f"rank_impressions: neg_ptr [I + 1], 0 <= row0, row0 + B <= I (row0 {row0}, B {B}, I {I})")
+    ptr = neg_ptr[row0:row0 + B + 1].long()
+    lens = ptr[1:] - ptr[:-1]
+    sp = (user * table.index_select(0, pos[row0:row0 + B].long())).sum(-1)
+    seg = torch.repeat_interleave(torch.arange(B), lens)
+    ids = negs[int(ptr[0]):int(ptr[-1])].long()
+    cmp = torch.zeros(3, B, dtype=torch.int64)  # gt, eq, nan
+    for s in range(0, ids.numel(), chunk):
+        sg = seg[s:s + chunk]
+        sc = (user.index_select(0, sg) * table.index_select(0, ids[s:s + chunk])).sum(-1)
+        p = sp.index_select(0, sg)
+        for r, m in enumerate((sc > p, sc == p, torch.isnan(sc))):
+            cmp[r].index_add_(0, sg, m.to(torch.int64))
+    cmp[2] += torch.isnan(sp).to(torch.int64)
+    return torch.stack([cmp[0], cmp[1], lens, cmp[2]], 1).to(torch.int32)

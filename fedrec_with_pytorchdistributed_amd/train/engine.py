@@ -41,7 +41,7 @@ from .. import ops
 from ..config import FedRecConfig
 from ..data.sampler import DeviceSampler, HostSampler, validation_batches
 from ..data.shard import Shard
-from ..eval.metrics import batch_metrics, topk_metrics
+from ..eval.metrics import batch_metrics, impression_means, impression_sums, topk_metrics
 from ..models.fedrec_model import FedRecModel
 from ..ops import functional as OF
 from ..ops import native
@@ -1156,3 +1156,71 @@ class LocalEngine:
         sc_h = host[n * k:].reshape(n, k)
         m = topk_metrics(ids_h, np.asarray(arr.pos[:n]))
         return (m, ids_h, sc_h) if return_lists else m
+
+    # ---- full-impression evaluation: the positive against EVERY negative the impression showed ----
+    def _full_valid_arrays(self):
+        """The validation corpus CSR ``(pos, neg_ptr, negs)`` on the engine's device (the device
+        sampler's arrays when it exists), built once; the ids are checked against the table size
+        here, on the host arrays -- the kernel trusts them."""
+        fv = getattr(self, "_fv_arrays", None)
+        if fv is None:
+            arr = self.shard.valid
+            for name, a in (("pos", arr.pos), ("neg_ids", arr.neg_ids)):
+                if len(a) and (int(np.max(a)) >= self.N or int(np.min(a)) < 0):
+                    raise ValueError(f"validate_full: valid.{name} holds ids outside [0, {self.N})")
+            vs = getattr(self, "_vsampler", None)
+            if vs is not None:
+                fv = (vs.pos, vs.neg_ptr, vs.negs)
+            else:
+                t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(self.device)
+                fv = (t(arr.pos, torch.int32), t(arr.neg_ptr, torch.int64),
+                      t(arr.neg_ids if len(arr.neg_ids) else np.zeros(1, np.int32), torch.int32))
+            self._fv_arrays = fv
+        return fv
+
+    @torch.no_grad()
+    def validate_full(self, batch_size: int = 256, limit: Optional[int] = None, return_counts: bool = False):
+        """Full-impression validation: each impression's positive is ranked against ALL of its
+        negatives (``ImpressionArrays.neg_ptr`` / ``neg_ids``), not the ``[pos] + negs[-4:]`` sample of
+        :meth:`validate` -- the protocol MIND's AUC / MRR / nDCG are quoted in, and the one under
+        which nDCG@5 and nDCG@10 differ.  Histories follow :meth:`validate`'s truncation rule; the
+        news table is built once; ``ops.rank_impressions`` leaves four integers per impression in one
+        ``[n, 4]`` device buffer and ONE copy brings it back for
+        :func:`eval.metrics.impression_metrics`.  -> ``full_valid_auc``, ``full_valid_mrr``,
+        ``full_val_ndcg@5``, ``full_val_ndcg@10``, ``n_full``, ``n_full_skipped`` (impressions
+        without a negative or with a NaN score), ``mean_candidates``; ``return_counts``: ``(metrics,
+        counts [n, 4] int32)``."""
+        self.sync_params()
+        arr = self.shard.valid
+        n = len(arr) if limit is None else min(int(limit), len(arr))
+        if n == 0:
+            m = full_valid_record(impression_sums(np.zeros((0, 4), np.int32)))
+            return (m, np.zeros((0, 4), np.int32)) if return_counts else m
+        table = self._catalog_table(None).float().contiguous()
+        truncate = not self.q.no_history_truncation
+        if self.device.type == "cuda" and self.fused_user and truncate:
+            self.prepare_validation(batch_size)
+            batches = (h for _, h in self._vsampler.valid_batches(batch_size, n))
+        else:
+            batches = (h for _, h in validation_batches(arr, batch_size, self.cfg.npratio, self.cfg.max_his_len,
+                                                        truncate, n))
+        pos, neg_ptr, negs = self._full_valid_arrays()
+        C = torch.empty(n, 4, dtype=torch.int32, device=self.device)
+        s0 = 0
+        for his in batches:
+            u = self.user_vectors(his, table)
+            B = u.shape[0]
+            C[s0:s0 + B].copy_(ops.rank_impressions(u, table, pos, neg_ptr, negs, s0))
+            s0 += B
+        counts = C.cpu().numpy()  # the one copy back
+        m = full_valid_record(impression_sums(counts))
+        return (m, counts) if return_counts else m
+
+
+def full_valid_record(sums: np.ndarray) -> Dict[str, float]:
+    """:func:`eval.metrics.impression_sums` (one client's, or the sum over clients) -> the
+    ``full_*`` keys of :meth:`LocalEngine.validate_full`."""
+    m = impression_means(sums)
+    return {"full_valid_auc": m["auc"], "full_valid_mrr": m["mrr"], "full_val_ndcg@5": m["ndcg5"],
+            "full_val_ndcg@10": m["ndcg10"], "n_full": m["n"], "n_full_skipped": m["n_skipped"],
+            "mean_candidates": m["mean_candidates"]}

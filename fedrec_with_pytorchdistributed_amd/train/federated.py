@@ -43,7 +43,8 @@ from ..privacy.rdp import calibrate_client_sigma
 from ..utils import obs
 from ..utils.fault import FaultInjector
 from . import checkpoint as ckpt
-from .engine import LocalEngine
+from ..eval.metrics import impression_sums
+from .engine import LocalEngine, full_valid_record
 
 METRIC_KEYS = ("training_loss", "validation_loss", "valid_auc", "valid_mrr", "val_ndcg@5", "val_ndcg@10")
 
@@ -93,6 +94,17 @@ def _reduce_metrics(ctx: DistContext, train: Dict, val: Dict) -> Dict:
     return {"training_loss": v[0].item() / steps, "validation_loss": v[3].item() / nv, "valid_auc": v[4].item() / nv,
             "valid_mrr": v[5].item() / nv, "val_ndcg@5": v[6].item() / nv, "val_ndcg@10": v[7].item() / nv,
             "impressions": v[2].item(), "epoch_s": t.item(), "impressions_per_s": v[2].item() / max(t.item(), 1e-9)}
+
+
+def _full_valid(ctx: DistContext, eng: LocalEngine, reduce: bool = True) -> Dict:
+    """``cfg.valid_full``: the full-impression validation of this client's split; with ``reduce``
+    the per-impression sums and counts of all clients travel in one packed all-reduce on the
+    control group (as :func:`_reduce_metrics`) -> the corpus-level ``full_*`` keys."""
+    _, counts = eng.validate_full(return_counts=True)
+    v = torch.from_numpy(impression_sums(counts))
+    if reduce and ctx.initialized and ctx.num_clients > 1:
+        dist.all_reduce(v, group=ctx.ctrl_group)
+    return full_valid_record(v.numpy())
 
 
 def _min_over_clients(ctx: DistContext, x: int) -> int:
@@ -249,6 +261,8 @@ def run_grad_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
         va = eng.validate()
         CHECK.verify(ctx.ctrl_group, f"grad_avg epoch {epoch}")
         last = _reduce_metrics(ctx, tr, va)
+        if cfg.valid_full:
+            last.update(_full_valid(ctx, eng))
         last.update({"epoch": epoch, "mode": "grad_avg", "clients": ctx.num_clients})
         if ctx.client_index == 0:
             writer.write(last)
@@ -308,6 +322,8 @@ def run_param_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
         va = eng.validate()
         CHECK.verify(ctx.ctrl_group, f"param_avg epoch {epoch}")
         last = _reduce_metrics(ctx, tr, va)
+        if cfg.valid_full:
+            last.update(_full_valid(ctx, eng))
         last.update({"epoch": epoch, "mode": "param_avg", "clients": W})
         if ctx.client_index == 0:
             writer.write(last)
@@ -423,6 +439,8 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
             beat()
             t1 = time.perf_counter()
             va = eng.validate()
+            if cfg.valid_full:  # this client's own split, like the rest of its round record
+                va = {**va, **_full_valid(ctx, eng, reduce=False)}
             beat()
             t_train += t1 - t0
             t_valid += time.perf_counter() - t1
