@@ -160,20 +160,42 @@ def _uid_name(shard, i: int) -> str:
 
 
 def main_recommend(argv: Optional[List[str]] = None):
-    """``recommend SNAPSHOT --data_dir=... --k=10 [--limit=N] [--out=recs.jsonl] [--key=value ...]``:
-    rank the whole catalog for every validation impression of the shard (single process, no
-    process group).  ``SNAPSHOT``: a snapshot of ``train/checkpoint.py``, or ``none`` for the freshly
-    initialised model.  Writes one JSON line per impression (``uid``, ``news``: the nid strings best
-    first, ``scores``) to ``--out`` (default: stdout); prints and returns the hr / ndcg / mrr metrics
-    as the final JSON line."""
+    """``recommend SNAPSHOT --data_dir=... --k=10 [--limit=N] [--out=recs.jsonl] [--diversity=L [--pool=P]]
+    [--key=value ...]``: rank the whole catalog for every validation impression of the shard (single
+    process, no process group).  ``SNAPSHOT``: a snapshot of ``train/checkpoint.py``, or ``none`` for
+    the freshly initialised model.  Writes one JSON line per impression (``uid``, ``news``: the nid
+    strings best first, ``scores``) to ``--out`` (default: stdout); prints and returns the hr / ndcg /
+    mrr metrics as the final JSON line.  ``--diversity=L`` (MMR's lambda, 0..1) re-ranks the ``--pool``
+    most relevant news (k..128; default ``min(128, max(4 k, 32))``) for diversity
+    (``LocalEngine.recommend``) and adds ``ild@k`` / ``coverage@k`` to the metrics; ``--diversity=1``
+    keeps the relevance lists and reports their diversity."""
     import json
 
     argv = sys.argv[1:] if argv is None else argv
-    own = {"k": "10", "limit": "", "out": "", "batch": "256"}
-    eng, shard = _offline_engine(
-        argv, own, "usage: recommend <snapshot|none> --data_dir=... [--k=10] [--limit=N] [--out=FILE] [--k=v]")
+    own = {"k": "10", "limit": "", "out": "", "batch": "256", "diversity": "", "pool": ""}
+    usage = ("usage: recommend <snapshot|none> --data_dir=... [--k=10] [--limit=N] [--out=FILE] "
+             "[--diversity=0..1 [--pool=k..128]] [--k=v]")
+    # the command's own numbers are checked before the engine is built
+    given = {a[2:].partition("=")[0]: a[2:].partition("=")[2] for a in argv if a.startswith("--")}
+    diversity = pool = None
+    try:
+        k = int(given.get("k", own["k"]))
+        if given.get("diversity", ""):
+            diversity = float(given["diversity"])
+        if given.get("pool", ""):
+            pool = int(given["pool"])
+    except ValueError:
+        raise SystemExit(usage)
+    if diversity is not None and not (0.0 <= diversity <= 1.0):
+        raise SystemExit(f"recommend: --diversity must lie in [0, 1] (got {given['diversity']})\n{usage}")
+    if pool is not None and diversity is None:
+        raise SystemExit(f"recommend: --pool needs --diversity\n{usage}")
+    if diversity is not None and not (1 <= k <= (k if pool is None else pool) <= 128):
+        raise SystemExit(f"recommend: --diversity needs 1 <= k <= pool <= 128 (got k {k}, pool {pool})\n{usage}")
+    eng, shard = _offline_engine(argv, own, usage)
     limit = int(own["limit"]) if own["limit"] else None
-    metrics, ids, scores = eng.recommend_valid(int(own["k"]), int(own["batch"]), limit, return_lists=True)
+    metrics, ids, scores = eng.recommend_valid(k, int(own["batch"]), limit, return_lists=True, diversity=diversity,
+                                               pool=pool)
     i2n = shard.index2nid
     f = open(own["out"], "w") if own["out"] else sys.stdout
     try:

@@ -170,3 +170,20 @@ def topk_metrics(ids: np.ndarray, pos: np.ndarray) -> Dict[str, float]:
     rank = np.where(found, hit.argmax(1) + 1, 1).astype(np.float64)
     return {f"hr@{k}": float(found.mean()), f"ndcg@{k}": float(np.where(found, 1.0 / np.log2(rank + 1.0), 0.0).mean()),
             f"mrr@{k}": float(np.where(found, 1.0 / rank, 0.0).mean()), "k": k, "n": int(ids.shape[0])}
+
+
+def diversity_metrics(ids: np.ndarray, ild: np.ndarray, n_catalog: int) -> Dict[str, float]:
+    """Beyond-accuracy quality of recommendation lists ``ids [n, k]`` (-1 = empty slot) with their
+    intra-list diversity ``ild [n]`` (``ops.mmr_rerank``: a list's mean pairwise ``1 - cos``):
+    ``ild@k``, the mean of ``ild`` over the lists with at least two items (NaN when there is none), and
+    ``coverage@k``, the distinct recommended ids divided by ``n_catalog``, the number of catalog rows
+    that were eligible for recommendation."""
+    ids = np.asarray(ids)
+    ild = np.asarray(ild, dtype=np.float64).reshape(-1)
+    k = int(ids.shape[1]) if ids.ndim == 2 else 0
+    if ids.ndim != 2 or ids.shape[0] == 0:
+        return {f"ild@{k}": float("nan"), f"coverage@{k}": float("nan")}
+    two = (ids >= 0).sum(1) >= 2
+    distinct = np.unique(ids[ids >= 0]).size
+    return {f"ild@{k}": float(ild[two].mean()) if two.any() else float("nan"),
+            f"coverage@{k}": float(distinct / n_catalog) if n_catalog > 0 else float("nan")}

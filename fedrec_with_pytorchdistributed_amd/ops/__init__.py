@@ -28,6 +28,9 @@ topk_scores           (beyond the reference)       topk_scores.hip: fp32 MFMA U 
 rank_impressions      (beyond the reference)       rank_impressions.hip: an impression's whole
                                                    negative list gathered, scored and compared
                                                    with its positive; 4 integers per impression
+mmr_rerank            (beyond the reference)       mmr_rerank.hip: a pool's rows gathered once, its
+                                                   P x P cosines on fp32 MFMA in registers, the
+                                                   greedy MMR picks and the list's ILD on the CU
 ====================  ===========================  ===========================================
 """
 from __future__ import annotations
@@ -254,6 +257,25 @@ def rank_impressions(user, table, pos, neg_ptr, negs, row0: int = 0):
         native.require_for(user)
         return torch.ops.fedrec_eval.rank_impressions(user, table, pos, neg_ptr, negs, int(row0))
     return ref.rank_impressions(user, table, pos, neg_ptr, negs, int(row0))
+
+
+def mmr_rerank(table, ids, rel, k: int, lam: float):
+    """Diversity re-rank of a candidate pool by Maximal Marginal Relevance -> ``(ids_out [B, k] int32,
+    rel_out [B, k] fp32, ild [B] fp32)``.  ``ids [B, P]`` int32 are rows of ``table [N, D]`` fp32 (``< 0``:
+    an empty slot -- what :func:`topk_scores` returns is a valid pool), ``rel [B, P]`` their relevance;
+    ``1 <= k <= P <= 128``, ``0 <= lam <= 1``.  Greedily, ``k`` times: pick the not-yet-picked slot with
+    the largest ``lam * rhat_j - (1 - lam) * max_{i picked} cos(row_i, row_j)``, ``rhat`` the pool's
+    relevance scaled to [0, 1]; ties go to the lowest pool position, so ``lam = 1`` returns the pool's
+    first ``k`` slots.  Outputs are in selection order (``rel_out``: the original ``rel``; ``(-1, -inf)``
+    past the valid count); ``ild`` is the list's mean pairwise ``1 - cos``.  The device kernel keeps
+    a user's whole cosine matrix in registers and is bitwise independent of the batch
+    (csrc/mmr_rerank.hip); ids are trusted to lie in ``[0, N)``.  The exact contract:
+    :func:`ops.reference.mmr_rerank`."""
+    if _dev(table):
+        native.require_for(table)
+        return tuple(torch.ops.fedrec_rerank.mmr_rerank(table, ids.to(torch.int32).contiguous(), rel.contiguous(),
+                                                         int(k), float(lam)))
+    return ref.mmr_rerank(table, ids, rel, int(k), float(lam))
 
 
 def segment_sum_rows(rows, inv, num_out: int, clip: float = 0.0, noise_std: float = 0.0,

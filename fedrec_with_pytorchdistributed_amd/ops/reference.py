@@ -395,3 +395,70 @@ def rank_impressions(user: torch.Tensor, table: torch.Tensor, pos: torch.Tensor,
             cmp[r].index_add_(0, sg, m.to(torch.int64))
     cmp[2] += torch.isnan(sp).to(torch.int64)
     return torch.stack([cmp[0], cmp[1], lens, cmp[2]], 1).to(torch.int32)
+
+
+# ---------------------------------------------------------------------------------------
+# Diversity re-rank (oracle of csrc/mmr_rerank.hip)
+# ---------------------------------------------------------------------------------------
+def mmr_rerank(table: torch.Tensor, ids: torch.Tensor, rel: torch.Tensor, k: int, lam: float,
+               chunk_elems: int = 1 << 24):
+    """Maximal Marginal Relevance over a candidate pool, in ``table``'s dtype -> ``(ids_out [B, k]
+    int32, rel_out [B, k], ild [B])``.  Slot ``j`` of ``ids [B, P]`` is valid iff ``ids[b, j] >= 0``;
+    ``rhat = (rel - min) / (max - min)`` over the valid slots (1 when ``max == min``); ``c_ij`` is the
+    cosine of table rows ``ids_i`` and ``ids_j`` (``g_ij / (sqrt(g_ii) * sqrt(g_jj))``, 0 unless both
+    norms are finite and positive and ``g_ij`` is finite).  Step ``t`` picks the not-yet-picked valid
+    slot with the largest ``m_j = lam * rhat_j - (1 - lam) * max_{i picked} c_ij`` (``lam * rhat_j`` at
+    ``t = 0``; a NaN ``m_j`` counts as ``-inf``; ties go to the lowest position).  Outputs are in
+    selection order, ``rel_out`` the picks' original ``rel``, ``(-1, -inf)`` past the valid count;
+    ``ild`` is the mean of ``1 - c_ij`` over the unordered pairs of picks (0 below two picks).  The
+    Gram is a row-wise ``(x_i * x_j).sum(-1)`` -- one summation order for every pair, so duplicate
+    rows tie bit for bit -- built for a few users at a time (``chunk_elems`` products at most)."""
+    B, P = ids.shape
+    D = table.shape[1]
+    k, dt = int(k), table.dtype
+    if not (1 <= k <= P) or not (0.0 <= float(lam) <= 1.0):
+        raise ValueError(f"mmr_rerank: 1 <= k <= P and 0 <= lam <= 1 (got k {k}, P {P}, lam {lam})")
+    valid = ids >= 0
+    relc = rel.to(dt)
+    inf = torch.full_like(relc, float("inf"))
+    mn = torch.where(valid, relc, inf).amin(1, keepdim=True)
+    mx = torch.where(valid, relc, -inf).amax(1, keepdim=True)
+    rhat = torch.where(mx == mn, torch.ones_like(relc), (relc - mn) / (mx - mn))
+    c = torch.empty(B, P, P, dtype=dt)
+    step = max(1, int(chunk_elems) // (P * P * D))
+    for s in range(0, B, step):
+        x = table.index_select(0, ids[s:s + step].clamp(min=0).reshape(-1).long()).view(-1, P, D)
+        g = (x[:, :, None, :] * x[:, None, :, :]).sum(-1)
+        d = g.diagonal(dim1=1, dim2=2)
+        ok = torch.isfinite(d) & (d > 0)
+        r = torch.sqrt(torch.where(ok, d, torch.ones_like(d)))
+        okk = ok[:, :, None] & ok[:, None, :] & torch.isfinite(g)
+        c[s:s + step] = torch.where(okk, g / (r[:, :, None] * r[:, None, :]), torch.zeros_like(g))
+    lam_t = torch.tensor(float(lam), dtype=dt)
+    oml = torch.ones((), dtype=dt) - lam_t
+    ids_out = torch.full((B, k), -1, dtype=torch.int32)
+    rel_out = torch.full((B, k), float("-inf"), dtype=rel.dtype)
+    alive = valid.clone()
+    picked = torch.zeros_like(valid)
+    ms = torch.zeros(B, P, dtype=dt)
+    ar, pos = torch.arange(B), torch.arange(P)[None, :]
+    for t in range(k):
+        m = lam_t * rhat - oml * ms if t > 0 else lam_t * rhat
+        m = torch.where(torch.isnan(m), torch.full_like(m, float("-inf")), m)
+        best = torch.where(alive, m, torch.full_like(m, float("-inf"))).amax(1, keepdim=True)
+        sel = torch.where(alive & (m == best), pos, torch.full_like(pos, P)).amin(1)
+        has = sel < P
+        sel = sel.clamp(max=P - 1)
+        ids_out[:, t] = torch.where(has, ids[ar, sel].to(torch.int32), ids_out[:, t])
+        rel_out[:, t] = torch.where(has, rel[ar, sel], rel_out[:, t])
+        hit = has[:, None] & (pos == sel[:, None])
+        alive &= ~hit
+        picked |= hit
+        csel = c[ar, :, sel]
+        ms = torch.where(has[:, None], torch.maximum(ms, csel) if t > 0 else csel, ms)
+    n_p = picked.sum(1)
+    pair = picked[:, :, None] & picked[:, None, :] & torch.ones(P, P, dtype=torch.bool).triu(1)[None]
+    tot = torch.where(pair, 1 - c, torch.zeros_like(c)).sum((1, 2))
+    npair = (n_p * (n_p - 1) // 2).to(dt)
+    ild = torch.where(n_p >= 2, tot / npair.clamp(min=1), torch.zeros_like(tot))
+    return ids_out, rel_out, ild

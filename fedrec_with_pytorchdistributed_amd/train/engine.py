@@ -41,7 +41,7 @@ from .. import ops
 from ..config import FedRecConfig
 from ..data.sampler import DeviceSampler, HostSampler, validation_batches
 from ..data.shard import Shard
-from ..eval.metrics import batch_metrics, impression_means, impression_sums, topk_metrics
+from ..eval.metrics import batch_metrics, diversity_metrics, impression_means, impression_sums, topk_metrics
 from ..models.fedrec_model import FedRecModel
 from ..ops import functional as OF
 from ..ops import native
@@ -1103,35 +1103,72 @@ class LocalEngine:
         his_v = table.index_select(0, his.reshape(-1).long()).view(B, H, -1)
         return self.model.user_encoder(his_v, his).float().contiguous()
 
+    @staticmethod
+    def mmr_pool(k: int, pool: Optional[int] = None) -> int:
+        """The candidate pool size of a diversity re-rank: ``pool``, else ``min(128, max(4 k, 32))``;
+        ``k <= pool <= 128`` (the re-rank kernel's bound) or ValueError."""
+        p = min(128, max(4 * int(k), 32)) if pool is None else int(pool)
+        if not (1 <= int(k) <= p <= 128):
+            raise ValueError(f"diversity re-rank needs 1 <= k <= pool <= 128 (got k {int(k)}, pool {p})")
+        return p
+
+    def _recommend(self, his, k, exclude_history, table, diversity, pool):
+        """:meth:`recommend` -> ``(ids, scores, ild)``; ``ild`` is None without ``diversity``."""
+        table = self._catalog_table(table)
+        his = self.to_device(his).to(torch.int32).contiguous()
+        u = self.user_vectors(his, table)
+        tab = table.float().contiguous()
+        if diversity is None:
+            scores, ids = ops.topk_scores(u, tab, int(k), his if exclude_history else None, 1)
+            return ids, scores, None
+        lam = float(diversity)
+        if not (0.0 <= lam <= 1.0):
+            raise ValueError(f"diversity must lie in [0, 1] (got {diversity})")
+        p = self.mmr_pool(k, pool)
+        scores, ids = ops.topk_scores(u, tab, p, his if exclude_history else None, 1)
+        return ops.mmr_rerank(tab, ids, scores, int(k), lam)
+
     @torch.no_grad()
-    def recommend(self, his, k: int = 10, exclude_history: bool = True,
-                  table: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def recommend(self, his, k: int = 10, exclude_history: bool = True, table: Optional[torch.Tensor] = None,
+                  diversity: Optional[float] = None, pool: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """The ``k`` best news of the whole catalog for each history -> ``(ids [B, k] int32, scores
         [B, k] fp32)``, best first (ties by ascending id; ``-1`` / ``-inf`` past the eligible count).
         The ``<unk>`` row 0 is never returned, nor -- with ``exclude_history`` -- anything the user
         clicked.  Scores are the raw dot products ``u . v`` (the model's sigmoid is monotone, so the
-        ranking is the model's).  One :meth:`encode_all` per call unless ``table`` is passed."""
-        table = self._catalog_table(table)
-        his = self.to_device(his).to(torch.int32).contiguous()
-        u = self.user_vectors(his, table)
-        scores, ids = ops.topk_scores(u, table.float().contiguous(), int(k), his if exclude_history else None, 1)
+        ranking is the model's).  One :meth:`encode_all` per call unless ``table`` is passed.
+
+        ``diversity`` (MMR's lambda in [0, 1]; None = off, the pure relevance ranking above): the
+        ``pool`` most relevant news (default :meth:`mmr_pool`) are re-ranked by
+        :func:`ops.mmr_rerank` -- relevance traded against the largest cosine similarity to what the
+        list already holds; the list is in selection order, the scores stay the picks' ``u . v``.
+        1.0 reproduces the relevance ranking."""
+        ids, scores, _ = self._recommend(his, k, exclude_history, table, diversity, pool)
         return ids, scores
 
     @torch.no_grad()
     def recommend_valid(self, k: int = 10, batch_size: int = 256, limit: Optional[int] = None,
-                        return_lists: bool = False):
+                        return_lists: bool = False, diversity: Optional[float] = None, pool: Optional[int] = None):
         """Full-catalog ranking quality over the validation impressions: each impression's history
         (truncated as in :meth:`validate`) ranks the catalog minus the history -- the held-out
         positive is not excluded -- and ``hr@k`` / ``ndcg@k`` / ``mrr@k`` of the positive come from
         :func:`eval.metrics.topk_metrics`.  The news table is built once, the per-batch lists stay
         in device buffers and ONE copy brings them back.  ``return_lists``: ``(metrics, ids, scores)``
-        with the ``[n, k]`` host arrays."""
+        with the ``[n, k]`` host arrays.  With ``diversity`` (see :meth:`recommend`) the lists are the
+        re-ranked ones and the metrics gain ``ild@k`` / ``coverage@k``
+        (:func:`eval.metrics.diversity_metrics`; the catalog is every row but ``<unk>``),
+        ``diversity`` and ``pool``; the per-list ILD values ride in the same copy."""
         self.sync_params()
         arr = self.shard.valid
         n = len(arr) if limit is None else min(int(limit), len(arr))
         k = int(k)
+        div = diversity is not None
+        extra = {"diversity": float(diversity), "pool": self.mmr_pool(k, pool)} if div else {}
+        if div and not (0.0 <= extra["diversity"] <= 1.0):
+            raise ValueError(f"diversity must lie in [0, 1] (got {diversity})")
         if n == 0:
             m = topk_metrics(np.zeros((0, k), np.int32), np.zeros(0, np.int32))
+            if div:
+                m.update(diversity_metrics(np.zeros((0, k), np.int32), np.zeros(0), 0), **extra)
             return (m, np.zeros((0, k), np.int32), np.zeros((0, k), np.float32)) if return_lists else m
         table = self._catalog_table(None).float().contiguous()
         truncate = not self.q.no_history_truncation
@@ -1143,18 +1180,23 @@ class LocalEngine:
                                                         truncate, n))
         IDS = torch.empty(n, k, dtype=torch.int32, device=self.device)
         SC = torch.empty(n, k, dtype=torch.float32, device=self.device)
+        ILD = torch.empty(n if div else 0, dtype=torch.float32, device=self.device)
         s0 = 0
         for his in batches:
-            ids, sc = self.recommend(his, k, True, table)
+            ids, sc, ild = self._recommend(his, k, True, table, diversity, pool)
             B = ids.shape[0]
             IDS[s0:s0 + B].copy_(ids)
             SC[s0:s0 + B].copy_(sc)
+            if div:
+                ILD[s0:s0 + B].copy_(ild)
             s0 += B
         # the one copy back (int32 ids ride along as raw bits of the fp32 buffer)
-        host = torch.cat([IDS.view(torch.float32).reshape(-1), SC.reshape(-1)]).cpu().numpy()
+        host = torch.cat([IDS.view(torch.float32).reshape(-1), SC.reshape(-1), ILD]).cpu().numpy()
         ids_h = host[:n * k].view(np.int32).reshape(n, k)
-        sc_h = host[n * k:].reshape(n, k)
+        sc_h = host[n * k:2 * n * k].reshape(n, k)
         m = topk_metrics(ids_h, np.asarray(arr.pos[:n]))
+        if div:
+            m.update(diversity_metrics(ids_h, host[2 * n * k:], table.shape[0] - 1), **extra)
         return (m, ids_h, sc_h) if return_lists else m
 
     # ---- full-impression evaluation: the positive against EVERY negative the impression showed ----
