@@ -153,6 +153,12 @@ class FedRecConfig:
     server_opt: str = "sgd"
     server_beta2: float = 0.99
     server_tau: float = 1e-3
+    # Byzantine-robust aggregation (Yin et al. 2018) in place of the mean, per coordinate over the
+    # clients: "trimmed_mean" drops the robust_trim lowest and highest values, "median" the
+    # (W - 1) // 2 on each side (ops.trimmed_mean; parallel/robust.py).  PA and both star
+    # aggregations; unweighted, and the server must see the individual updates
+    robust_agg: str = "none"  # none | trimmed_mean | median
+    robust_trim: int = 1
     pa_average_moments: bool = False  # PA: average the clients' Adam m / v with the parameters
     # unfrozen backbone (GA): reduce the gradient in ~28 MB buckets during the backward (DDP's
     # reducer, parallel/reducer.py); False = one flat all-reduce after it

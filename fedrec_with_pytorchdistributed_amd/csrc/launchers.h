@@ -192,6 +192,9 @@ int fr_rank_impressions(const float* user, const float* table, const int* pos, c
 int fr_mmr_rerank(const float* table, const int* ids, const float* rel, int* ids_out, float* rel_out, float* ild,
                   long B, long N, int P, int D, int k, float lam, hipStream_t s);
 
+// ---- robust_agg.hip --------------------------------------------------------------------------
+int fr_trimmed_mean(const float* stack, float* out, long long* dropped, int W, long n, int trim, hipStream_t s);
+
 // ---- secagg.hip ------------------------------------------------------------------------------
 int fr_secagg_mask(const float* x, int* out, long n, float scale, float clipv, const unsigned long long* seeds,
                    const int* signs, int npeers, unsigned long long round, hipStream_t s);

@@ -31,6 +31,9 @@ rank_impressions      (beyond the reference)       rank_impressions.hip: an impr
 mmr_rerank            (beyond the reference)       mmr_rerank.hip: a pool's rows gathered once, its
                                                    P x P cosines on fp32 MFMA in registers, the
                                                    greedy MMR picks and the list's ILD on the CU
+trimmed_mean          (beyond the reference)       robust_agg.hip: W <= 32 clients' values of a
+                                                   coordinate sorted in registers (compile-time
+                                                   network), trimmed mean / median + dropped counts
 ====================  ===========================  ===========================================
 """
 from __future__ import annotations
@@ -276,6 +279,22 @@ def mmr_rerank(table, ids, rel, k: int, lam: float):
         return tuple(torch.ops.fedrec_rerank.mmr_rerank(table, ids.to(torch.int32).contiguous(), rel.contiguous(),
                                                          int(k), float(lam)))
     return ref.mmr_rerank(table, ids, rel, int(k), float(lam))
+
+
+def trimmed_mean(stack, trim: int):
+    """Coordinate-wise trimmed mean of ``W <= 32`` clients' vectors -> ``(out [n] fp32, dropped [W]
+    int64)``: ``stack [W, n]`` fp32 contiguous, ``0 <= 2 trim < W``.  Per coordinate the ``trim`` lowest
+    and ``trim`` highest values (ranked by a total order on the floats' bits, -0.0 < +0.0 < ... < +inf <
+    NaN, ties to the lower client) are dropped and the rest averaged in rank order; ``trim = (W - 1)
+    // 2`` is the median, ``trim = 0`` the plain mean in client order.  ``dropped[c]`` counts the
+    coordinates where client ``c`` was cut.  The device kernel reads each value once, sorts in
+    registers and writes ``n`` floats; both results are bitwise independent of its grid and of how a
+    caller splits the coordinates into calls (csrc/robust_agg.hip).  The exact contract:
+    :func:`ops.reference.trimmed_mean`."""
+    if _dev(stack):
+        native.require_for(stack)
+        return tuple(torch.ops.fedrec_agg.trimmed_mean(stack, int(trim)))
+    return ref.trimmed_mean(stack, int(trim))
 
 
 def segment_sum_rows(rows, inv, num_out: int, clip: float = 0.0, noise_std: float = 0.0,

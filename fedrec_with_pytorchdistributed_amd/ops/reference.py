@@ -462,3 +462,70 @@ def mmr_rerank(table: torch.Tensor, ids: torch.Tensor, rel: torch.Tensor, k: int
     npair = (n_p * (n_p - 1) // 2).to(dt)
     ild = torch.where(n_p >= 2, tot / npair.clamp(min=1), torch.zeros_like(tot))
     return ids_out, rel_out, ild
+
+
+# ---------------------------------------------------------------------------------------
+# Byzantine-robust aggregation (oracle of csrc/robust_agg.hip)
+# ---------------------------------------------------------------------------------------
+def trimmed_mean_check(stack: torch.Tensor, trim: int) -> None:
+    """The argument checks of ``fedrec_agg::trimmed_mean``, with its messages."""
+    op = "fedrec_agg::trimmed_mean"
+    if stack.dtype != torch.float32:
+        raise RuntimeError(f"{op}: stack must be fp32")
+    if stack.dim() != 2:
+        raise RuntimeError(f"{op}: stack [W, n] (got {stack.dim()} dims)")
+    if not stack.is_contiguous():
+        raise RuntimeError(f"{op}: stack must be contiguous")
+    W, n = stack.shape
+    if not (1 <= W <= 32 and n >= 1):
+        raise RuntimeError(f"{op}: 1 <= W <= 32, n >= 1 (got W {W}, n {n})")
+    if not (0 <= 2 * trim < W):
+        raise RuntimeError(f"{op}: 0 <= 2 * trim < W (got trim {trim}, W {W})")
+
+
+def order_keys(x: torch.Tensor) -> torch.Tensor:
+    """The monotone uint32 image of fp32 ``x`` (as int64): NaN -> 0xFFFFFFFF, sign bit set ->
+    ``~bits``, else ``bits | 0x80000000``; so -inf < ... < -0.0 < +0.0 < ... < +inf < NaN."""
+    b = x.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    k = torch.where(b >= 0x80000000, 0xFFFFFFFF - b, b | 0x80000000)
+    return torch.where(torch.isnan(x), torch.full_like(k, 0xFFFFFFFF), k)
+
+
+def trimmed_mean(stack: torch.Tensor, trim: int, acc_dtype: Optional[torch.dtype] = None, chunk: int = 1 << 20):
+    """Coordinate-wise trimmed mean of ``stack [W, n]`` fp32 (1 <= W <= 32, 0 <= 2 trim < W) ->
+    ``(out [n], dropped [W] int64)``.
+
+    ``trim > 0``: a coordinate's W values are ranked by ``(order_keys(x), client index)`` -- a total
+    order (ties go to the lower client; not ``torch.sort`` on floats, which does not tell -0.0 from
+    +0.0).  ``out`` is the sum of ranks ``trim .. W - trim - 1`` in ascending rank order, added left to
+    right from the first kept value, then one division by ``W - 2 trim``; a NaN or inf among the kept
+    ranks propagates.  ``dropped[c]`` counts the coordinates where client ``c`` ranked among the
+    ``trim`` lowest or ``trim`` highest (they sum to ``2 trim n``).  ``trim = (W - 1) // 2`` is the
+    median.  ``trim = 0``: nothing is ranked; ``out`` is the sum in CLIENT order over ``W`` -- the
+    plain mean bit for bit -- and ``dropped`` is zero.
+
+    Sums and the division run in ``acc_dtype`` (default fp32, the device kernel's arithmetic; fp64
+    gives the tests' reference).  At most ``chunk`` columns are ranked at a time."""
+    trim = int(trim)
+    trimmed_mean_check(stack, trim)
+    W, n = stack.shape
+    dt = acc_dtype or torch.float32
+    m = W - 2 * trim
+    out = torch.empty(n, dtype=dt)
+    dropped = torch.zeros(W, dtype=torch.int64)
+    div = torch.full((1,), float(m), dtype=dt)
+    client = torch.arange(W, dtype=torch.int64)[:, None]
+    for s in range(0, n, chunk):
+        x = stack[:, s:s + chunk]
+        if trim == 0:
+            v = x.to(dt)
+        else:
+            idx = torch.sort(order_keys(x) * 32 + client, dim=0).values & 31
+            v = torch.gather(x, 0, idx).to(dt)[trim:W - trim]
+            cut = torch.cat([idx[:trim], idx[W - trim:]]).reshape(-1)
+            dropped += torch.bincount(cut, minlength=W)
+        acc = v[0].clone()
+        for r in range(1, m):
+            acc = acc + v[r]
+        out[s:s + chunk] = acc / div.expand_as(acc)
+    return out, dropped

@@ -73,6 +73,15 @@ def allreduce_(tensors: List[torch.Tensor], group, op=dist.ReduceOp.SUM, scale: 
                 t.copy_(s)
 
 
+def allgather_stack(flat: torch.Tensor, group, W: int) -> torch.Tensor:
+    """Every member's contiguous 1-D ``flat`` (the same length and dtype on each) -> ``[W, len]``, row
+    ``c`` from the group's member ``c``."""
+    CHECK.record("all_gather", flat, f"W={W}")
+    out = flat.new_empty(W * flat.numel())  # the concatenated form: every backend takes it
+    dist.all_gather_into_tensor(out, flat, group=group)
+    return out.view(W, flat.numel())
+
+
 def broadcast_(tensors: List[torch.Tensor], src: int, group, bucket_bytes: int = BUCKET_BYTES) -> None:
     for b in _buckets(tensors, bucket_bytes):
         if len(b) == 1 and b[0].is_contiguous():

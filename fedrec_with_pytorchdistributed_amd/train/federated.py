@@ -15,6 +15,11 @@
                    ``allreduce`` aggregation, the clients average among themselves over RCCL
                    and only the result goes to the coordinator.
 
+``cfg.robust_agg`` (``trimmed_mean`` | ``median``, parallel/robust.py) replaces the mean of
+``run_param_avg`` and of both star aggregations with the coordinate-wise robust rule: the
+all-reduces become all-gathers, and the records gain ``dropped_share`` (how often each client's
+value was cut).
+
 All modes write ``snapshot.pt`` in the reference layout (rank 0 / coordinator, atomic) and
 JSONL metrics with the reference's metric names.
 """
@@ -37,6 +42,7 @@ from ..parallel import catalog, comm
 from ..parallel import secagg
 from ..parallel.collcheck import CHECK
 from ..parallel.control import ControlPlane, Heartbeat
+from ..parallel.robust import RobustRule
 from ..parallel.dist import (DistContext, data_ipc, make_bucket_reducer, make_grad_allreduce, make_secure_grad_allreduce,
                              selfcheck)
 from ..privacy.rdp import calibrate_client_sigma
@@ -231,6 +237,7 @@ class ServerStep:
 
 # ---------------------------------------------------------------------------------------
 def run_grad_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
+    RobustRule.from_cfg(cfg, "grad_avg")  # (an active rule is rejected here)
     selfcheck(ctx, log=obs.log)
     shard = load_client_shard(cfg, ctx)
     model = build_model(cfg, ctx.device)
@@ -274,6 +281,7 @@ def run_grad_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
 
 
 def run_param_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
+    rule = RobustRule.from_cfg(cfg, "param_avg")
     selfcheck(ctx, log=obs.log)
     shard = load_client_shard(cfg, ctx)
     model = build_model(cfg, ctx.device)
@@ -294,7 +302,10 @@ def run_param_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
     K = cfg.param_avg_every if sched == "per_step" else 0
     steps = _min_over_clients(ctx, eng.sampler.num_batches()) if K else None
 
-    ipc = data_ipc(ctx, cfg.collective_timeout_s) if ctx.device.type == "cuda" else None
+    ipc = data_ipc(ctx, cfg.collective_timeout_s) if ctx.device.type == "cuda" and not rule.active else None
+    if rule.active:
+        rule.trim_for(W)  # an impossible rule fails before the first step
+    cut = {"dropped": torch.zeros(W, dtype=torch.int64), "n": 0}  # since the last record
 
     def average():
         if ctx.initialized and W > 1:
@@ -302,8 +313,13 @@ def run_param_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
             ts = model.sync_tensors(full)
             if cfg.pa_average_moments:  # the clients' Adam moments averaged with the parameters
                 ts = ts + [model.flat.m, model.flat.v]
-            with obs.range("param_allreduce"):
-                comm.allreduce_(ts, ctx.data_group, scale=1.0 / W, ipc=ipc)
+            if rule.active:  # every client combines the same stack: bitwise-same aggregates
+                with obs.range("param_allgather"):
+                    cut["dropped"] += rule.gather_combine_(ts, ctx.data_group, W)
+                cut["n"] += sum(t.numel() for t in ts)
+            else:
+                with obs.range("param_allreduce"):
+                    comm.allreduce_(ts, ctx.data_group, scale=1.0 / W, ipc=ipc)
             if anchor is not None:  # server step on the mean (same inputs on every client)
                 with torch.no_grad():
                     model.flat.flat.copy_(server.apply(anchor, model.flat.flat))
@@ -325,6 +341,10 @@ def run_param_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
         if cfg.valid_full:
             last.update(_full_valid(ctx, eng))
         last.update({"epoch": epoch, "mode": "param_avg", "clients": W})
+        if rule.active and cut["n"]:
+            last.update(rule.record(cut["dropped"], cut["n"], W))
+            cut["dropped"].zero_()
+            cut["n"] = 0
         if ctx.client_index == 0:
             writer.write(last)
             obs.log(f"[param_avg] epoch {epoch}: " + ", ".join(f"{k}={last[k]:.4f}" for k in METRIC_KEYS))
@@ -359,7 +379,10 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
     model = build_model(cfg, ctx.device)  # created ONCE: Adam moments persist across rounds
     eng = LocalEngine(cfg, model, shard, ctx.device, rank=ctx.rank, grad_allreduce=None)
     fault = FaultInjector("client", k)
+    rule = RobustRule.from_cfg(cfg, "fedavg_star")
     agg = _aggregation(cfg, ctx)
+    if rule.active and agg == "allreduce":
+        rule.trim_for(ctx.num_clients)
     full = cfg.sync == "full"
     writer = _metrics_writer(cfg, False)
     # secure aggregation: pairwise seeds by Diffie-Hellman over the control plane
@@ -452,7 +475,14 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
             ckpt.save_state_dict(os.path.join(_artifact_dir(cfg), sub, "model.pt"), model)
         beat(force=True)
         fault.before_upload(r, up)
-        if agg == "allreduce":
+        if agg == "allreduce" and rule.active:
+            # the clients gather each other's uploads and every one of them combines the same stack
+            dropped = rule.gather_combine_([up], ctx.data_group, ctx.num_clients)
+            if k == 0:
+                cp.put_tensor(f"r{r}/avg", up.cpu())
+                meta["dropped"] = [int(x) for x in dropped]
+            cp.put_json(f"r{r}/meta/{k}", meta)
+        elif agg == "allreduce":
             w = float(len(shard.train)) if cfg.weighted_fedavg else 1.0
             wt = torch.tensor([w], device=up.device, dtype=torch.float32)
             up.mul_(wt)
@@ -522,6 +552,7 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
     W = ctx.num_clients
     model = build_model(cfg, torch.device("cpu"))
     server = ServerStep.from_cfg(cfg)  # off by default: the plain mean
+    rule = RobustRule.from_cfg(cfg, "fedavg_star")
     start_round = 0
     if cfg.snapshot_path and os.path.exists(cfg.snapshot_path):
         info = ckpt.load_snapshot(cfg.snapshot_path, model)
@@ -541,11 +572,14 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
             cp.put_tensor(f"r{r}/backbone", _flat_backbone(model))
         cp.set(f"r{r}/go", "1")
         dead: List[int] = []
+        dropped = None  # robust rule: how often each ACCEPTED client's value was cut
         if agg == "allreduce":
             avg = cp.get_tensor(f"r{r}/avg", cfg.round_timeout_s)
             metas = [cp.get_json(f"r{r}/meta/{k}") for k in range(W)]
             accepted = list(range(W))
             new = avg
+            if rule.active:
+                dropped = metas[0].get("dropped")
         else:
             keys = {k: f"r{r}/up/{k}" for k in range(W)}
             present, dead = cp.wait_uploads(keys, need, cfg.round_timeout_s, cfg.heartbeat_timeout_s,
@@ -580,6 +614,12 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
                 if new is None:
                     obs.log(f"[server] round {r}: a client's update is non-finite; the global model is kept")
                     new = model.flat.flat.detach().clone()
+            elif rule.active:
+                try:
+                    rule.trim_for(len(ups))
+                except ValueError as e:  # like a missed quorum: too few updates left to rank
+                    raise RuntimeError(f"round {r}: {e} ({len(accepted)}/{W} accepted); aborting")
+                new, dropped = rule.combine(torch.stack([t.float() for t in ups]))
             else:
                 acc = torch.zeros_like(ups[0], dtype=torch.float64)
                 for t, w in zip(ups, weights):
@@ -592,6 +632,10 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
             model.flat.flat.copy_(new)
         dt = time.perf_counter() - t0
         rec = {"round": r, "clients_accepted": len(accepted), "clients": W, "clients_dead": dead, "round_s": dt}
+        if rule.active and dropped is not None:  # one share per client; a client not accepted has none
+            by = dict(zip(accepted, rule.record(dropped, new.numel(), len(accepted))["dropped_share"]))
+            rec.update({"robust_agg": rule.kind, "robust_trim": rule.trim_for(len(accepted)),
+                        "dropped_share": [by.get(k) for k in range(W)]})
         for key in ("training_loss", "validation_loss", "valid_auc", "valid_mrr", "val_ndcg@5", "val_ndcg@10",
                     "train_s", "valid_s"):
             vals = [m[key] for m in metas if key in m]

@@ -5,7 +5,9 @@
 * ``kill``  -- the process exits immediately (a client vanishing mid-round);
 * ``hang``  -- the process stops making progress (sleeps), like a wedged peer;
 * ``nan``   -- the client's upload is poisoned with NaNs;
-* ``slow:<s>`` -- sleep ``s`` seconds before uploading (a straggler).
+* ``slow:<s>`` -- sleep ``s`` seconds before uploading (a straggler);
+* ``scale:<f>`` -- the client's upload is multiplied by ``f`` (a model-poisoning client: wrong but
+  finite, so the non-finite check lets it through; ``--robust_agg`` is the defence).
 
 Example: ``FEDREC_FAULT=client:1:round:2:kill,client:0:round:3:nan``.  The coordinator must
 answer with a quorum aggregation (or a clean abort) within ``round_timeout_s`` -- never the
@@ -64,3 +66,5 @@ class FaultInjector:
             time.sleep(r.arg)
         if r.action == "nan" and flat is not None:
             flat.fill_(float("nan"))
+        if r.action == "scale" and flat is not None:
+            flat.mul_(r.arg)
