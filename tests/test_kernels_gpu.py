@@ -134,6 +134,7 @@ def test_title_attention_launch_variants(dev, waves, n, T):
 @pytest.mark.parametrize("dtype,D,Q", [(torch.bfloat16, 768, 384), (torch.float32, 400, 200), (torch.bfloat16, 64, 32),
                                        (torch.bfloat16, 512, 256)])
 def test_additive_pool(dev, dtype, D, Q):
+    # per element, masked, eps-dominated and fused forms: tests/test_user_oracle_gpu.py
     n, T = 23, 50
     x = torch.randn(n, T, D, device=dev).to(dtype)
     e = torch.tanh(torch.randn(n, T, Q, device=dev)).to(dtype)
@@ -166,6 +167,7 @@ def test_user_attention(dev, H):
     to 1e-5 against the fp32 oracle forward AND backward; H > 64 runs the long-history kernels
     (online softmax over 64-row LDS chunks): the reference never truncates histories (Q6; its
     shipped shard has H = 76)."""
+    # per element, masked, eps-dominated and fused forms: tests/test_user_oracle_gpu.py
     B, NH, DK = 7, 20, 20
     qkv = torch.randn(B, H, 3 * NH * DK, device=dev)
     ctx, stats = ops.user_attention_fwd(qkv, NH, DK)
@@ -244,6 +246,7 @@ def test_additive_pool_long_fp32(dev, T):
 @pytest.mark.parametrize("variant", [1, 0])  # 1: block per impression (default), 0: wave per impression
 @pytest.mark.parametrize("act,C", [("sigmoid", 5), ("identity", 5), ("sigmoid", 16), ("identity", 1)])
 def test_score_ce(dev, variant, act, C):
+    # per element, masked, eps-dominated and fused forms: tests/test_user_oracle_gpu.py
     B, D = 33, 400
     cand = torch.randn(B, C, D, device=dev) * 0.1
     u = torch.randn(B, D, device=dev) * 0.1
