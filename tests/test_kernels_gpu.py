@@ -3,6 +3,10 @@
 bf16 kernels are compared with tolerances scaled to bf16 rounding; fp32 kernels tightly.
 The GEMM family (gemm_bf16.hip) is judged here by whole-output norms only; its per-element check
 against the fp64 oracle is tests/test_gemm_oracle_gpu.py.
+The LayerNorm file (layernorm.hip: every forward form, the backward, the streaming GELU) and the
+gradient reductions (train_grad.hip: colsum, gelu_bwd_colsum, embed_grad) likewise: their
+per-element check against the fp64 oracle, at the shapes where their loops take a second trip, is
+tests/test_norm_oracle_gpu.py.
 """
 import math
 
