@@ -137,9 +137,9 @@ __device__ __forceinline__ void load_raw(const GemmDesc& g, bool isA, int r0, in
 
 // The same tile with no data-dependent branches around loads (FAST launches: every contiguous extent a
 // multiple of 8 elements, 16-byte aligned rows): each 8-element half of a chunk is one
-// unconditional load from its address or -- when it lies outside the operand -- from the
-// operand's first row, and `vm` records which halves are real; the zeroing select waits until
-// the chunk is stored to LDS, after the MFMAs.  (With per-lane branches around the loads the
+// unconditional load from its address or -- when it lies outside the operand -- from an offset
+// past the buffer descriptor's range (OOB), which the buffer unit answers with zeros: no mask, no
+// select, the zeros arrive as data.  (With per-lane branches around the loads the
 // compiler joins the paths right after them and waits for the data there: every k-tile's
 // loads became synchronous -- the 128-row tiles measured 2-4x SLOWER than 64-row ones.)
 // (1) offsets: every chunk's two half byte offsets into its operand -- any row-gather index

@@ -1,6 +1,7 @@
 """csrc/small_gemm.hip against an fp32 torch emulation (operands rounded to bf16 as the kernel
 does): every layout, the fused row gather / Philox dropout prologues, the dropout epilogue,
-bias / tanh / accumulate, and several GEMMs per launch; plus the deterministic fp32 colsum."""
+bias / tanh / accumulate, and several GEMMs per launch; plus the deterministic fp32 colsum.
+Per element against an fp64 oracle, every launch form: tests/test_sgemm_oracle_gpu.py."""
 
 import pytest
 import torch

@@ -1,5 +1,6 @@
 """Weight-gradient TN GEMM (csrc/gemm_wgrad.hip) against an fp32 torch reference of the same
-bf16 operands: dW = dy^T x over a long reduction dim, partial tiles in every dimension."""
+bf16 operands: dW = dy^T x over a long reduction dim, partial tiles in every dimension.
+Per element at small M (stage counts, the split rule): tests/test_sgemm_oracle_gpu.py."""
 import pytest
 import torch
 
