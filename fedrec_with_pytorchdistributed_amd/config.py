@@ -159,6 +159,10 @@ class FedRecConfig:
     # aggregations; unweighted, and the server must see the individual updates
     robust_agg: str = "none"  # none | trimmed_mean | median
     robust_trim: int = 1
+    # star clients upload only the ceil(upload_topk * n) largest-magnitude coordinates of their round
+    # delta and keep the rest as a residual added to the next round's delta (top-k sparsification
+    # with error feedback; ops.topk_delta / ops.sparse_combine, parallel/sparsify.py).  0 = dense
+    upload_topk: float = 0.0
     pa_average_moments: bool = False  # PA: average the clients' Adam m / v with the parameters
     # unfrozen backbone (GA): reduce the gradient in ~28 MB buckets during the backward (DDP's
     # reducer, parallel/reducer.py); False = one flat all-reduce after it

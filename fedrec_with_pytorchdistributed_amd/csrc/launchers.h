@@ -195,6 +195,13 @@ int fr_mmr_rerank(const float* table, const int* ids, const float* rel, int* ids
 // ---- robust_agg.hip --------------------------------------------------------------------------
 int fr_trimmed_mean(const float* stack, float* out, long long* dropped, int W, long n, int trim, hipStream_t s);
 
+// ---- sparse_delta.hip ------------------------------------------------------------------------
+long fr_topk_delta_ws(long n);  // workspace of fr_topk_delta in 32-bit words
+int fr_topk_delta(const float* local, const float* global, float* residual, int* idx, float* val, unsigned* ws, long n,
+                  long k, hipStream_t s);
+int fr_sparse_combine(const float* base, const int* idx, const float* val, const float* weights, float* out, int W,
+                      long k, long n, hipStream_t s);
+
 // ---- secagg.hip ------------------------------------------------------------------------------
 int fr_secagg_mask(const float* x, int* out, long n, float scale, float clipv, const unsigned long long* seeds,
                    const int* signs, int npeers, unsigned long long round, hipStream_t s);

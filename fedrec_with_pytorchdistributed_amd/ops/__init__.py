@@ -34,6 +34,10 @@ mmr_rerank            (beyond the reference)       mmr_rerank.hip: a pool's rows
 trimmed_mean          (beyond the reference)       robust_agg.hip: W <= 32 clients' values of a
                                                    coordinate sorted in registers (compile-time
                                                    network), trimmed mean / median + dropped counts
+topk_delta /          (beyond the reference)       sparse_delta.hip: exact magnitude top-k of one long
+sparse_combine                                     row by radix select (no sort, no host sync) with
+                                                   the error-feedback residual; W sparse lists
+                                                   scattered onto a base through LDS tiles
 ====================  ===========================  ===========================================
 """
 from __future__ import annotations
@@ -295,6 +299,35 @@ def trimmed_mean(stack, trim: int):
         native.require_for(stack)
         return tuple(torch.ops.fedrec_agg.trimmed_mean(stack, int(trim)))
     return ref.trimmed_mean(stack, int(trim))
+
+
+def topk_delta(local, global_, residual, k: int):
+    """Magnitude top-k of a round delta with error feedback -> ``(idx [k] int32 ascending, val [k]
+    fp32)``; ``residual`` is updated in place.  ``local``, ``global_``, ``residual`` ``[n]`` fp32
+    contiguous (a view such as ``x[1:]`` is fine), ``residual`` overlapping neither input, ``1 <= k <= n
+    < 2^31``.  ``a = (local - global_) + residual``; the ``k`` coordinates with the largest ``bits(a) &
+    0x7fffffff`` are sent (NaN above inf above every finite value, the lower index among equal keys),
+    and ``residual`` becomes ``+0.0`` there and ``a`` elsewhere.  The device path is a radix select
+    with no sort and no host synchronisation, bitwise independent of its grid
+    (csrc/sparse_delta.hip).  The exact contract: :func:`ops.reference.topk_delta`."""
+    if _dev(residual):
+        native.require_for(residual)
+        return tuple(torch.ops.fedrec_sparse.topk_delta(local, global_, residual, int(k)))
+    return ref.topk_delta(local, global_, residual, int(k))
+
+
+def sparse_combine(base, idx, val, weights):
+    """``W`` sparse updates applied to ``base [n]`` fp32 -> ``out [n]``: ``out = base + (sum over c, in
+    client order, of weights[c] * scatter(idx[c], val[c])) / sum(weights)``.  ``idx [W, k]`` int32 with
+    every row strictly ascending in ``[0, n)`` (callers validate with
+    :func:`ops.reference.sparse_upload_check`; the kernel stays in bounds whatever the content),
+    ``val [W, k]`` fp32, ``weights [W]`` fp32.  Every product, sum and the division is rounded on its
+    own, so the device kernel (csrc/sparse_delta.hip) and the host oracle hold the same bits.  The
+    exact contract: :func:`ops.reference.sparse_combine`."""
+    if _dev(base):
+        native.require_for(base)
+        return torch.ops.fedrec_sparse.combine(base, idx, val, weights)
+    return ref.sparse_combine(base, idx, val, weights)
 
 
 def segment_sum_rows(rows, inv, num_out: int, clip: float = 0.0, noise_std: float = 0.0,

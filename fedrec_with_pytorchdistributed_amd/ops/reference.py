@@ -529,3 +529,129 @@ def trimmed_mean(stack: torch.Tensor, trim: int, acc_dtype: Optional[torch.dtype
             acc = acc + v[r]
         out[s:s + chunk] = acc / div.expand_as(acc)
     return out, dropped
+
+
+# ---------------------------------------------------------------------------------------
+# Top-k sparsified uploads with error feedback (oracle of csrc/sparse_delta.hip)
+# ---------------------------------------------------------------------------------------
+def _overlaps(a: torch.Tensor, b: torch.Tensor) -> bool:
+    pa, pb = a.data_ptr(), b.data_ptr()
+    return pa < pb + b.numel() * b.element_size() and pb < pa + a.numel() * a.element_size()
+
+
+def _check_vec(t: torch.Tensor, op: str, name: str) -> None:
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{op}: {name} must be fp32")
+    if t.dim() != 1:
+        raise RuntimeError(f"{op}: {name} [n] (got {t.dim()} dims)")
+    if not t.is_contiguous():
+        raise RuntimeError(f"{op}: {name} must be contiguous")
+
+
+def topk_delta_check(local: torch.Tensor, global_: torch.Tensor, residual: torch.Tensor, k: int) -> None:
+    """The argument checks of ``fedrec_sparse::topk_delta``, with its messages."""
+    op = "fedrec_sparse::topk_delta"
+    _check_vec(local, op, "local")
+    _check_vec(global_, op, "global")
+    _check_vec(residual, op, "residual")
+    n = local.numel()
+    if not (global_.numel() == n and residual.numel() == n):
+        raise RuntimeError(f"{op}: local, global and residual must have one length (got {n}, {global_.numel()}, "
+                           f"{residual.numel()})")
+    if not (1 <= n < 2 ** 31):
+        raise RuntimeError(f"{op}: 1 <= n < 2^31 (got n {n})")
+    if not (1 <= k <= n):
+        raise RuntimeError(f"{op}: 1 <= k <= n (got k {k}, n {n})")
+    if not (local.device == residual.device and global_.device == residual.device):
+        raise RuntimeError(f"{op}: local, global and residual must be on one device")
+    if _overlaps(residual, local) or _overlaps(residual, global_):
+        raise RuntimeError(f"{op}: residual must not overlap local or global")
+
+
+def magnitude_keys(a: torch.Tensor) -> torch.Tensor:
+    """``bits(a) & 0x7fffffff`` of fp32 ``a`` as int32 (never negative, so it compares as the uint32
+    does): +-0 lowest, inf above every finite value, every NaN above inf, ``+x`` and ``-x`` tie."""
+    return a.contiguous().view(torch.int32) & 0x7FFFFFFF
+
+
+def topk_delta(local: torch.Tensor, global_: torch.Tensor, residual: torch.Tensor, k: int):
+    """Magnitude top-k with error feedback -> ``(idx [k] int32, val [k] fp32)``; ``residual`` is
+    updated in place.
+
+    ``a = (local - global_) + residual`` (one fp32 subtraction, one fp32 addition).  The selected set
+    is the first ``k`` entries of a STABLE descending sort of ``magnitude_keys(a)``: the k largest
+    magnitudes, NaN above inf above every finite value, the lower index among equal keys.  ``idx`` is
+    that set in strictly ascending order, ``val = a[idx]`` (the bits of ``a``, a NaN's payload
+    included), and afterwards ``residual`` is ``+0.0`` at ``idx`` and ``a`` elsewhere: what is not sent
+    now is added to the next round's delta."""
+    k = int(k)
+    topk_delta_check(local, global_, residual, k)
+    a = (local - global_) + residual
+    order = torch.sort(magnitude_keys(a), descending=True, stable=True).indices[:k]
+    idx = torch.sort(order).values
+    val = a[idx].clone()
+    residual.copy_(a)
+    residual[idx] = 0.0
+    return idx.to(torch.int32), val
+
+
+def sparse_combine_check(base: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, weights: torch.Tensor) -> None:
+    """The argument checks of ``fedrec_sparse::combine``, with its messages."""
+    op = "fedrec_sparse::combine"
+    _check_vec(base, op, "base")
+    if idx.dtype != torch.int32:
+        raise RuntimeError(f"{op}: idx must be int32")
+    if val.dtype != torch.float32:
+        raise RuntimeError(f"{op}: val must be fp32")
+    if not (idx.dim() == 2 and val.dim() == 2 and idx.shape == val.shape):
+        raise RuntimeError(f"{op}: idx and val [W, k] of one shape")
+    if not (idx.is_contiguous() and val.is_contiguous()):
+        raise RuntimeError(f"{op}: idx and val must be contiguous")
+    _check_vec(weights, op, "weights")
+    n, (W, k) = base.numel(), idx.shape
+    if not (1 <= n < 2 ** 31):
+        raise RuntimeError(f"{op}: 1 <= n < 2^31 (got n {n})")
+    if not (1 <= W <= 65536 and weights.numel() == W):
+        raise RuntimeError(f"{op}: 1 <= W <= 65536 and weights [W] (got W {W}, weights {weights.numel()})")
+    if not (1 <= k <= n):
+        raise RuntimeError(f"{op}: 1 <= k <= n (got k {k}, n {n})")
+    if not (idx.device == base.device and val.device == base.device and weights.device == base.device):
+        raise RuntimeError(f"{op}: base, idx, val and weights must be on one device")
+
+
+def sparse_combine(base: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+    """``W`` sparse lists scattered onto ``base [n]`` -> ``out [n]`` fp32.  ``idx [W, k]`` int32, each row
+    strictly ascending in ``[0, n)`` (the caller's check: :func:`sparse_upload_check`), ``val [W, k]``,
+    ``weights [W]``.  ``acc`` starts at ``+0.0``; for ``c = 0 .. W - 1`` in that order ``acc[idx[c]] +=
+    weights[c] * val[c]`` (the product and the sum rounded separately); ``wsum`` is the sequential fp32
+    sum of the weights from ``+0.0``; ``out = base + acc / wsum`` at every coordinate."""
+    sparse_combine_check(base, idx, val, weights)
+    acc = torch.zeros_like(base)
+    ws = torch.zeros((), dtype=torch.float32)
+    for c in range(idx.shape[0]):
+        ix = idx[c].long()
+        acc[ix] = acc[ix] + weights[c] * val[c]
+        ws = ws + weights[c]
+    return base + acc / ws
+
+
+def sparse_upload_check(idx: torch.Tensor, val: torch.Tensor, n: int, k: int) -> None:
+    """A sparse upload as :func:`topk_delta` makes it: ``idx`` int32 ``[k]`` strictly ascending within
+    ``[0, n)``, ``val`` fp32 ``[k]``.  Raises ``ValueError`` naming the first violation."""
+    if idx.dtype != torch.int32:
+        raise ValueError(f"sparse upload: idx must be int32 (got {idx.dtype})")
+    if val.dtype != torch.float32:
+        raise ValueError(f"sparse upload: val must be fp32 (got {val.dtype})")
+    if idx.dim() != 1 or idx.numel() != k:
+        raise ValueError(f"sparse upload: idx must have length {k} (got shape {tuple(idx.shape)})")
+    if val.dim() != 1 or val.numel() != k:
+        raise ValueError(f"sparse upload: val must have length {k} (got shape {tuple(val.shape)})")
+    i = idx.long()
+    bad = ((i < 0) | (i >= n)).nonzero()
+    if bad.numel():
+        j = int(bad[0])
+        raise ValueError(f"sparse upload: idx[{j}] = {int(i[j])} is outside [0, {n})")
+    bad = (i[1:] <= i[:-1]).nonzero()
+    if bad.numel():
+        j = int(bad[0]) + 1
+        raise ValueError(f"sparse upload: idx is not strictly ascending at {j} ({int(i[j - 1])} then {int(i[j])})")

@@ -102,18 +102,26 @@ def client_snapshot_path(snapshot_path: str, client: int) -> str:
     return os.path.join(d, f"client{client}_{f}")
 
 
-def save_client_state(path: str, model: FedRecModel, round_idx: int, engine: Dict[str, int]) -> None:
+def save_client_state(path: str, model: FedRecModel, round_idx: int, engine: Dict[str, int],
+                      residual: Optional[torch.Tensor] = None) -> None:
     """A star client's resume state: the trainable flat parameters, Adam moments + step, RNG
     states and engine counters -- NOT the frozen backbone (the round's global model and the
-    client's own seed / checkpoint restore that).  ~14 MB instead of a 270 MB state_dict."""
+    client's own seed / checkpoint restore that).  ~14 MB instead of a 270 MB state_dict.
+    ``residual``: the error-feedback residual of sparsified uploads (``cfg.upload_topk``), stored
+    under ``UPLOAD_RESIDUAL``; without it the snapshot has no such key."""
     snap: Dict[str, Any] = {"FLAT_PARAMS": model.flat.flat.detach().cpu(), "OPTIM_STATE": model.flat.state(),
                             "ROUND": int(round_idx), "ENGINE": {k: int(v) for k, v in engine.items()},
                             "FLAT_NAMES": list(model.flat.names)}
+    if residual is not None:
+        snap["UPLOAD_RESIDUAL"] = residual.detach().cpu()
     snap.update(rng_state())
     atomic_save(snap, path)
 
 
-def load_client_state(path: str, model: FedRecModel) -> Dict[str, Any]:
+def load_client_state(path: str, model: FedRecModel, residual: Optional[torch.Tensor] = None) -> Dict[str, Any]:
+    """Restore a client's state.  ``residual`` (when given) takes the snapshot's ``UPLOAD_RESIDUAL``; a
+    snapshot without the key, or with another length, leaves it zero (``residual_restored`` in the
+    returned record tells which)."""
     snap = torch.load(path, map_location="cpu", weights_only=True)
     if "FLAT_PARAMS" not in snap:  # a full snapshot (round-2 format)
         return load_snapshot(path, model)
@@ -123,7 +131,13 @@ def load_client_state(path: str, model: FedRecModel) -> Dict[str, Any]:
         model.flat.flat.copy_(snap["FLAT_PARAMS"].to(model.flat.flat.device))
     model.flat.load_state(snap["OPTIM_STATE"])
     restore_rng(snap)
-    return {"round": snap.get("ROUND"), "engine": snap.get("ENGINE", {})}
+    restored = False
+    if residual is not None:
+        saved = snap.get("UPLOAD_RESIDUAL")
+        restored = saved is not None and saved.numel() == residual.numel()
+        with torch.no_grad():
+            residual.copy_(saved.to(residual.device, torch.float32)) if restored else residual.zero_()
+    return {"round": snap.get("ROUND"), "engine": snap.get("ENGINE", {}), "residual_restored": restored}
 
 
 def save_state_dict(path: str, model: FedRecModel) -> None:

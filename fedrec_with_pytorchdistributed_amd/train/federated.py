@@ -20,6 +20,11 @@
 all-reduces become all-gathers, and the records gain ``dropped_share`` (how often each client's
 value was cut).
 
+``cfg.upload_topk`` (parallel/sparsify.py) makes a star client upload only the largest-magnitude
+fraction of its round delta and keep the rest as a residual for the next round (top-k
+sparsification with error feedback); both star aggregations scatter the sparse lists onto the
+round's global model, and the records gain ``upload_bytes`` / ``dense_bytes``.
+
 All modes write ``snapshot.pt`` in the reference layout (rank 0 / coordinator, atomic) and
 JSONL metrics with the reference's metric names.
 """
@@ -38,11 +43,13 @@ from ..config import FedRecConfig
 from ..data.shard import Shard
 from ..data.synthetic import SynthSpec, SyntheticCorpus
 from ..models.fedrec_model import FedRecModel
+from .. import ops
 from ..parallel import catalog, comm
 from ..parallel import secagg
 from ..parallel.collcheck import CHECK
-from ..parallel.control import ControlPlane, Heartbeat
+from ..parallel.control import ControlPlane, Heartbeat, encode_tensor
 from ..parallel.robust import RobustRule
+from ..parallel.sparsify import Sparsifier
 from ..parallel.dist import (DistContext, data_ipc, make_bucket_reducer, make_grad_allreduce, make_secure_grad_allreduce,
                              selfcheck)
 from ..privacy.rdp import calibrate_client_sigma
@@ -238,6 +245,7 @@ class ServerStep:
 # ---------------------------------------------------------------------------------------
 def run_grad_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
     RobustRule.from_cfg(cfg, "grad_avg")  # (an active rule is rejected here)
+    Sparsifier.from_cfg(cfg, "grad_avg")  # (and sparsified uploads: star only)
     selfcheck(ctx, log=obs.log)
     shard = load_client_shard(cfg, ctx)
     model = build_model(cfg, ctx.device)
@@ -282,6 +290,7 @@ def run_grad_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
 
 def run_param_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
     rule = RobustRule.from_cfg(cfg, "param_avg")
+    Sparsifier.from_cfg(cfg, "param_avg")  # (an active sparsifier is rejected here: star only)
     selfcheck(ctx, log=obs.log)
     shard = load_client_shard(cfg, ctx)
     model = build_model(cfg, ctx.device)
@@ -380,6 +389,9 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
     eng = LocalEngine(cfg, model, shard, ctx.device, rank=ctx.rank, grad_allreduce=None)
     fault = FaultInjector("client", k)
     rule = RobustRule.from_cfg(cfg, "fedavg_star")
+    sparse = Sparsifier.from_cfg(cfg, "fedavg_star")
+    # what top-k sparsification has not sent yet (error feedback); zero at the start
+    residual = torch.zeros_like(model.flat.flat, dtype=torch.float32) if sparse.active else None
     agg = _aggregation(cfg, ctx)
     if rule.active and agg == "allreduce":
         rule.trim_for(ctx.num_clients)
@@ -402,9 +414,12 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
         obs.log(f"[client {k}] save_every={cfg.save_every} does not apply to client snapshots: they are written "
                 "every round (a resume from an older round would redraw LDP noise / dropout already uploaded)")
     if csnap and os.path.exists(csnap):
-        info = ckpt.load_client_state(csnap, model)
+        info = ckpt.load_client_state(csnap, model, residual)
         eng.load_state(info["engine"])
         obs.log(f"[client {k}] resumed {csnap} (round {info['round']}, Adam step {model.flat.step})")
+        if sparse.active and not info.get("residual_restored"):
+            obs.log(f"[client {k}] {csnap} holds no upload residual of {residual.numel()} elements: resuming with a "
+                    "zero residual")
     beat = Heartbeat(cp, f"client{k}", cfg.heartbeat_s)
     # model sync (server.py:76-77 / client.py:261-264): client 0 alone reads the coordinator's
     # global model from the store and broadcasts it over the client data group (RCCL over
@@ -450,7 +465,8 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
         before = _backbone_before(model, full)
         _receive_global(cp, r, model, ctx, full, bcast)
         _backbone_synced(model, full, before)
-        theta_g = model.flat.flat.detach().clone() if secure is not None else None  # the round's global model
+        # the round's global model
+        theta_g = model.flat.flat.detach().clone() if secure is not None or sparse.active else None
         eng.ensure_cache()  # after the broadcast every client is here: the collective build point
         eng.sigma = _maybe_dp(cfg, eng)
         eng.epoch = 0
@@ -475,7 +491,24 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
             ckpt.save_state_dict(os.path.join(_artifact_dir(cfg), sub, "model.pt"), model)
         beat(force=True)
         fault.before_upload(r, up)
-        if agg == "allreduce" and rule.active:
+        if sparse.active:
+            idx, val = sparse.compress(up, theta_g.float(), residual)
+            if not bool(torch.isfinite(val).all()):
+                # sent as it is (the coordinator rejects it); nothing of it may come back next round
+                residual.zero_()
+            blob = encode_tensor(sparse.pack(idx, val))
+            meta.update({"upload_k": int(idx.numel()), "upload_bytes": len(blob)})
+            if agg == "allreduce":
+                # the clients gather each other's lists and every one of them scatters the same W lists
+                w = float(len(shard.train)) if cfg.weighted_fedavg else 1.0
+                new = ops.sparse_combine(theta_g.float().contiguous(),
+                                         *sparse.gather(idx, val, w, ctx.data_group, ctx.num_clients, up.numel()))
+                if k == 0:
+                    cp.put_tensor(f"r{r}/avg", new.cpu())
+            else:
+                cp.set(f"r{r}/up/{k}", blob)
+            cp.put_json(f"r{r}/meta/{k}", meta)
+        elif agg == "allreduce" and rule.active:
             # the clients gather each other's uploads and every one of them combines the same stack
             dropped = rule.gather_combine_([up], ctx.data_group, ctx.num_clients)
             if k == 0:
@@ -508,7 +541,7 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
             # full state with the frozen backbone).  Every round, not every save_every: a resume
             # from an older round would redraw the LDP noise / dropout of the rounds in between
             # at the same offsets, and noise that was already uploaded must never be reused
-            ckpt.save_client_state(csnap, model, r, eng.state())
+            ckpt.save_client_state(csnap, model, r, eng.state(), residual)
         last = meta
         r += 1
     _dump_flat(model, ctx)
@@ -553,6 +586,7 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
     model = build_model(cfg, torch.device("cpu"))
     server = ServerStep.from_cfg(cfg)  # off by default: the plain mean
     rule = RobustRule.from_cfg(cfg, "fedavg_star")
+    sparse = Sparsifier.from_cfg(cfg, "fedavg_star")
     start_round = 0
     if cfg.snapshot_path and os.path.exists(cfg.snapshot_path):
         info = ckpt.load_snapshot(cfg.snapshot_path, model)
@@ -585,21 +619,28 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
             present, dead = cp.wait_uploads(keys, need, cfg.round_timeout_s, cfg.heartbeat_timeout_s,
                                             log=lambda m: obs.log(f"[server] round {r}: {m}"))
             ups, metas, accepted = [], [], []
+            n_flat = model.flat.flat.numel()
             for key in present:
                 k = int(key.rsplit("/", 1)[1])
                 try:
                     t = cp.get_tensor(key)
                     meta = cp.get_json(f"r{r}/meta/{k}", 30.0)
+                    if sparse.active:  # (idx, val); a malformed list drops the client like a corrupt blob
+                        t = sparse.unpack(t, n_flat, sparse.k_for(n_flat))
                 except Exception as e:  # corrupt blob / missing meta -> drop this client
                     obs.log(f"[server] round {r}: dropping client {k}: {e}")
                     continue
-                if not cfg.secagg.enabled and not torch.isfinite(t).all():
+                if not cfg.secagg.enabled and not torch.isfinite(t[1] if sparse.active else t).all():
                     obs.log(f"[server] round {r}: client {k} sent non-finite parameters; rejected")
                     continue
                 ups.append(t)
                 metas.append(meta)
                 accepted.append(k)
-                if cfg.round_artifacts and not cfg.secagg.enabled:  # server.py:27 received_model_{k}.pt
+                if sparse.active:
+                    if cfg.round_artifacts:  # that client's model as far as its upload tells
+                        ckpt.atomic_save(ckpt.flat_to_state_dict(model, sparse.scatter(model.flat.flat, *t)),
+                                         os.path.join(_artifact_dir(cfg), f"received_model_{k}.pt"))
+                elif cfg.round_artifacts and not cfg.secagg.enabled:  # server.py:27 received_model_{k}.pt
                     ckpt.atomic_save(ckpt.flat_to_state_dict(model, t),
                                      os.path.join(_artifact_dir(cfg), f"received_model_{k}.pt"))
             if cfg.secagg.enabled and len(accepted) != W:
@@ -614,6 +655,9 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
                 if new is None:
                     obs.log(f"[server] round {r}: a client's update is non-finite; the global model is kept")
                     new = model.flat.flat.detach().clone()
+            elif sparse.active:
+                new = sparse.combine(model.flat.flat.detach().float(), [u[0] for u in ups], [u[1] for u in ups],
+                                     weights)
             elif rule.active:
                 try:
                     rule.trim_for(len(ups))
@@ -636,6 +680,8 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
             by = dict(zip(accepted, rule.record(dropped, new.numel(), len(accepted))["dropped_share"]))
             rec.update({"robust_agg": rule.kind, "robust_trim": rule.trim_for(len(accepted)),
                         "dropped_share": [by.get(k) for k in range(W)]})
+        if sparse.active:
+            rec.update(sparse.record(new.numel(), [int(m.get("upload_bytes", 0)) for m in metas]))
         for key in ("training_loss", "validation_loss", "valid_auc", "valid_mrr", "val_ndcg@5", "val_ndcg@10",
                     "train_s", "valid_s"):
             vals = [m[key] for m in metas if key in m]
