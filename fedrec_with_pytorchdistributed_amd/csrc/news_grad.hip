@@ -14,6 +14,18 @@
 // occurrence row, so it does not depend on which wave processes it.  The default float4 chunk
 // pass applies the clip + noise as it loads each occurrence row (one launch + the edge fix-up);
 // the separate per-occurrence pass (ldp_rows_kernel) remains for the other forms.
+//
+// Noise counter layouts.  Element d of occurrence row r takes one normal of one Philox call (words
+// x, y -> components 0, 1; words z, w -> components 2, 3).  There are TWO layouts, and the same
+// (seed, offset) gives a different noise field in each:
+//   fused  (segsum_chunk4_kernel<., true> / segsum_chunk4_ldp_kernel):
+//            counter (r << 16) | (d / 4),               component d % 4
+//   rows   (ldp_rows_kernel; d = lane + 64 kk):
+//            counter (r << 16) | (2 lane + kk / 4),     component kk % 4
+// fr_segment_sum_rows_ldp takes the fused form when the variant is 2, D % 4 == 0 and rows, out and
+// scratch are 16-byte aligned; every other case (variant 0 or 1, D % 4 != 0, a misaligned view)
+// runs ldp_rows_kernel and then the plain sum.  Both are held element by element to an fp64
+// oracle in tests/test_data_oracle_gpu.py (tests/data_oracle.py states the layouts again).
 #include "common.h"
 #include "launchers.h"
 

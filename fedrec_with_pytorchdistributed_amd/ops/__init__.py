@@ -340,6 +340,13 @@ def segment_sum_rows(rows, inv, num_out: int, clip: float = 0.0, noise_std: floa
     the layout dedup produces: every output row has occurrences, except trailing padded rows
     (``zero_empty``, the step graphs' padded unique lists).  ``dev_off`` (device int64[1]):
     added to ``offset`` on the device, so a captured step graph draws fresh noise per replay.
+
+    Device noise: element ``d`` of occurrence row ``r`` is one normal of Philox(``seed``, ``offset`` +
+    ``dev_off``) in one of two counter layouts -- the same seed gives a different field in each.
+    The fused float4 chunk pass (segsum variant 2, ``D % 4 == 0``, 16-byte aligned rows) uses counter
+    ``(r << 16) | d // 4``, component ``d % 4``; every other case (variant 0 or 1, ``D % 4 != 0``, a
+    misaligned view) runs the two-pass fallback with counter ``(r << 16) | (2 * (d % 64) + d // 256)``,
+    component ``(d // 64) % 4`` (csrc/news_grad.hip; the oracle: tests/data_oracle.py).
     """
     if _dev(rows):
         if seg is None:

@@ -278,14 +278,14 @@ def score_ce_fwd_bwd(cand: torch.Tensor, user: torch.Tensor, act: str = "sigmoid
 def segment_sum_rows(rows: torch.Tensor, inv: torch.Tensor, num_out: int,
                      clip: float = 0.0, noise_std: float = 0.0,
                      generator: Optional[torch.Generator] = None) -> torch.Tensor:
-    """``out[inv[r]] += clip_r(rows[r]) + N(0, noise_std)`` -> ``[num_out, D]`` (fp32)."""
+    """``out[inv[r]] += clip_r(rows[r]) + N(0, noise_std)`` -> ``[num_out, D]`` (fp32; fp64 for fp64 rows)."""
     g = _f(rows)
     if clip > 0:
         nrm = g.norm(dim=1, keepdim=True)
         g = g * torch.clamp(clip / (nrm + 1e-12), max=1.0)
     if noise_std > 0:
-        g = g + torch.randn(g.shape, generator=generator, device=g.device) * noise_std
-    out = torch.zeros(num_out, g.shape[1], dtype=torch.float32, device=g.device)
+        g = g + torch.randn(g.shape, generator=generator, device=g.device).to(g.dtype) * noise_std
+    out = torch.zeros(num_out, g.shape[1], dtype=g.dtype, device=g.device)
     out.index_add_(0, inv.long(), g)
     return out
 

@@ -267,6 +267,7 @@ def test_score_ce(dev, variant, act, C):
 @pytest.mark.parametrize("num_news", [500, 3 << 20])  # 32-bit sort keys / the 64-bit form (ids >= 2^19)
 @pytest.mark.parametrize("R", [64 * 55, 37, 1024, 128 * 55, 8192])  # register-bitonic slots E = 4, 1, 1, 8, 8
 def test_dedup_and_segment_sum(dev, num_news, R):
+    # exact, at the key-range, run-edge and chunk-grid edges, per element: tests/test_data_oracle_gpu.py
     # (64-bit keys at P = 8192 would need a 128 KB two-buffer key image: the LDS form runs those)
     ids = torch.randint(0, num_news, (R,), device=dev, dtype=torch.int32)
     ids[::7] = ids[3]  # repeated ids: the occurrence order inside a segment must be ascending
@@ -293,6 +294,7 @@ def test_segment_sum_skewed(dev, variant, R, D):
     singletons; R not a multiple of the 16-row chunk): chunked form (1, default) and the
     block-per-row form (0) against an fp64 index_add, bitwise reproducible run to run; the float4
     chunk pass (2, default) is bitwise the scalar one (1)."""
+    # per element, segments placed on the chunk grid, every form and width: tests/test_data_oracle_gpu.py
     g = torch.Generator().manual_seed(R + D)
     ids = torch.multinomial(1.0 / torch.arange(1, 600, dtype=torch.float64), R, replacement=True, generator=g)
     ids[torch.rand(R, generator=g) < 0.3] = 0
@@ -343,6 +345,7 @@ def test_segment_sum_ldp_block_form_matches_wave_form(dev, R, D):
 
 
 def test_ldp_noise_statistics(dev):
+    # every element against the draw of its own counter, both layouts, clip + noise: tests/test_data_oracle_gpu.py
     R, D = 4096, 400
     rows = torch.zeros(R, D, device=dev)
     inv = torch.arange(R, device=dev, dtype=torch.int32)
@@ -493,6 +496,7 @@ def test_gemm_variants(dev, variant, M, N, K, act, res, bias):
 
 
 def test_device_sampler_semantics(dev):
+    # bit for bit against an exact twin of the sampler: tests/test_data_oracle_gpu.py
     import numpy as np
     from fedrec_with_pytorchdistributed_amd.data.sampler import DeviceSampler
     from fedrec_with_pytorchdistributed_amd.data.synthetic import make_client_shards
