@@ -77,17 +77,6 @@ FRAC_BITS = 16
 CLIP = 1024.0
 
 
-def frac_bits_for(world: int, bound: float) -> int:
-    """Fraction bits of the fixed-point grid for ``world`` clients whose coordinates are
-    clamped to ``[-bound, bound]``: the largest ``f`` with ``world * bound * 2^f <= 2^30``,
-    so the int32 sum of every client's quantised value cannot wrap (masks aside).  The same
-    rule as the device kernels' ``frac_exp2`` (``secagg.hip``)."""
-    import math
-
-    f = int(math.floor(math.log2((2.0 ** 30) / (max(1, int(world)) * max(float(bound), 1e-30)))))
-    return max(0, min(f, 56))
-
-
 def quantize_ref(x: torch.Tensor, frac_bits: int = FRAC_BITS, clip: float = CLIP) -> torch.Tensor:
     return torch.round(x.float().clamp(-clip, clip) * (2.0 ** frac_bits)).to(torch.int64).to(torch.int32)
 
@@ -188,8 +177,8 @@ class ExactMasker:
        W-client sum cannot wrap int32), pairwise masks, one int32 SUM all-reduce; the masks
        cancel exactly and the dequantised sum is the plain sum to within ``W 2^(-f-1)``.
 
-    Nothing is clamped, so there is no running bound to collapse or to lag a gradient spike
-    (round 3's ``RunningMasker``).  A non-finite coordinate anywhere makes every output NaN,
+    Nothing is clamped: the bound is agreed afresh for every sum, so it can neither collapse
+    nor lag a gradient spike, as a bound carried over from earlier steps could.  A non-finite coordinate anywhere makes every output NaN,
     as the plain sum would be non-finite.  Two collectives per call, both on the caller's
     stream."""
 
@@ -207,11 +196,16 @@ class ExactMasker:
     def allreduce_(self, g: torch.Tensor, round_idx: int, group, check_tag: str = "secagg", ipc=None) -> None:
         """``g`` <- the exact (fixed-point) SUM of every client's ``g``, in place.  ``ipc``: an
         :class:`.ipc_allreduce.IpcAllReduce` moves both int32 buffers instead of ``group``."""
+        flat = g.reshape(-1)
+        self._allreduce_flat_(flat, round_idx, group, check_tag, ipc)
+        if flat.untyped_storage().data_ptr() != g.untyped_storage().data_ptr():
+            g.copy_(flat.view_as(g))  # ``g`` has no 1-D view (e.g. a column block): reshape copied it
+
+    def _allreduce_flat_(self, flat: torch.Tensor, round_idx: int, group, check_tag: str, ipc) -> None:
         import torch.distributed as dist
 
         from .collcheck import CHECK
 
-        flat = g.reshape(-1)
         hround = _HIST_ROUND | int(round_idx)
         if flat.is_cuda:
             from ..ops import native
