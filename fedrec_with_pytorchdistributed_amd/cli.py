@@ -14,6 +14,13 @@ node) join one c10d rendezvous; roles come from the entrypoint, never from rank 
 For a one-invocation single-node star run, ``python -m fedrec_with_pytorchdistributed_amd.cli
 star <rounds> <epochs> <batch> [--k=v]`` under ``torchrun --nproc-per-node W+1`` makes rank 0
 the coordinator and ranks 1..W the GPU clients.
+
+Star upload compression (both off by default, both with an error-feedback residual kept in the client
+snapshot): ``--upload_topk=F`` sends the ``k = max(1, ceil(F n))`` largest-magnitude coordinates of the
+round delta (``8 k`` bytes instead of ``4 n``); ``--upload_bits=8`` / ``--upload_bits=4`` sends stochastic
+8- or 4-bit codes with one fp32 scale per 256 coordinates (``n bits / 8 + 4 ceil(n / 256)`` bytes; with
+``--upload_topk`` as well ``4 k + k bits / 8 + 4 ceil(k / 256)``).  Neither combines with
+``--secagg.enabled=1``, ``--robust_agg`` or the averaging modes.
 """
 from __future__ import annotations
 

@@ -163,6 +163,11 @@ class FedRecConfig:
     # delta and keep the rest as a residual added to the next round's delta (top-k sparsification
     # with error feedback; ops.topk_delta / ops.sparse_combine, parallel/sparsify.py).  0 = dense
     upload_topk: float = 0.0
+    # star clients upload their round delta as stochastic 8- or 4-bit codes with one fp32 scale per 256
+    # coordinates and keep the quantisation error as a residual added to the next round's delta (block
+    # quantisation with error feedback; ops.quantize_delta / ops.dequant_combine, parallel/quantize.py);
+    # with upload_topk the selected values are quantised.  0 = fp32 values
+    upload_bits: int = 0
     pa_average_moments: bool = False  # PA: average the clients' Adam m / v with the parameters
     # unfrozen backbone (GA): reduce the gradient in ~28 MB buckets during the backward (DDP's
     # reducer, parallel/reducer.py); False = one flat all-reduce after it

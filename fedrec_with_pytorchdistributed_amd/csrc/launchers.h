@@ -202,6 +202,12 @@ int fr_topk_delta(const float* local, const float* global, float* residual, int*
 int fr_sparse_combine(const float* base, const int* idx, const float* val, const float* weights, float* out, int W,
                       long k, long n, hipStream_t s);
 
+// ---- quant_delta.hip -------------------------------------------------------------------------
+int fr_quantize_delta(const float* local, const float* global, float* residual, unsigned char* codes, float* scales,
+                      long n, int bits, unsigned long long seed, unsigned long long offset, hipStream_t s);
+int fr_dequant_combine(const float* base, const unsigned char* codes, const float* scales, const float* weights,
+                       float* out, int W, long n, int bits, hipStream_t s);
+
 // ---- secagg.hip ------------------------------------------------------------------------------
 int fr_secagg_mask(const float* x, int* out, long n, float scale, float clipv, const unsigned long long* seeds,
                    const int* signs, int npeers, unsigned long long round, hipStream_t s);

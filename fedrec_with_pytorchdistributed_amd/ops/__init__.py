@@ -38,6 +38,10 @@ topk_delta /          (beyond the reference)       sparse_delta.hip: exact magni
 sparse_combine                                     row by radix select (no sort, no host sync) with
                                                    the error-feedback residual; W sparse lists
                                                    scattered onto a base through LDS tiles
+quantize_delta /      (beyond the reference)       quant_delta.hip: stochastic int8 / int4 codes with one
+dequant_combine                                    fp32 scale per 256 coordinates and the error-feedback
+                                                   residual, 16 coordinates per lane in registers; W
+                                                   quantised deltas dequantised onto a base
 ====================  ===========================  ===========================================
 """
 from __future__ import annotations
@@ -328,6 +332,43 @@ def sparse_combine(base, idx, val, weights):
         native.require_for(base)
         return torch.ops.fedrec_sparse.combine(base, idx, val, weights)
     return ref.sparse_combine(base, idx, val, weights)
+
+
+def quantize_delta(local, global_, residual, bits: int, seed: int, offset: int):
+    """Stochastic block quantisation of a round delta with error feedback -> ``(codes uint8 [ceil(n bits /
+    8)], scales fp32 [ceil(n / 256)])``; ``residual`` is updated in place.  ``local``, ``global_``,
+    ``residual`` ``[n]`` fp32 contiguous (a view such as ``x[1:]`` is fine), ``residual`` overlapping neither
+    input, ``1 <= n < 2^31``, ``bits`` 8 or 4.  ``a = (local - global_) + residual``; each block of 256
+    coordinates gets the scale ``max|a| / Q`` (``Q = 2^(bits - 1) - 1``) and every coordinate the code
+    ``clamp(floor(a / s) + up, -Q, Q)``, rounded up with probability ``frac(a / s)`` by the Philox stream
+    ``(seed, offset)``; ``residual`` becomes ``a - code * s``.  A block with an inf or a NaN sends a NaN
+    scale, zero codes and keeps a zero residual.  Bitwise independent of the grid
+    (csrc/quant_delta.hip).  The exact contract: :func:`ops.reference.quantize_delta`."""
+    if _dev(residual):
+        native.require_for(residual)
+        return tuple(torch.ops.fedrec_quant.quantize_delta(local, global_, residual, int(bits), int(seed), int(offset)))
+    return ref.quantize_delta(local, global_, residual, int(bits), int(seed), int(offset))
+
+
+def dequant_combine(base, codes, scales, weights, bits: int):
+    """``W`` quantised updates applied to ``base [n]`` fp32 -> ``out [n]``: ``out = base + (sum over c, in
+    client order, of weights[c] * (code[c] * scale[c])) / sum(weights)``.  ``codes [W, ceil(n bits / 8)]``
+    uint8, ``scales [W, ceil(n / 256)]`` fp32 (callers validate with
+    :func:`ops.reference.quant_upload_check`; the kernel stays in bounds whatever the content),
+    ``weights [W]`` fp32.  Every product, sum and the division is rounded on its own, so the device kernel
+    (csrc/quant_delta.hip) and the host oracle hold the same bits.  The exact contract:
+    :func:`ops.reference.dequant_combine`."""
+    if _dev(base):
+        native.require_for(base)
+        return torch.ops.fedrec_quant.dequant_combine(base, codes, scales, weights, int(bits))
+    return ref.dequant_combine(base, codes, scales, weights, int(bits))
+
+
+def dequantize(codes, scales, bits: int, n: int):
+    """One upload's delta ``[n]`` fp32 from ``codes [ceil(n bits / 8)]`` and ``scales [ceil(n / 256)]``:
+    :func:`dequant_combine` with ``W = 1``, a zero base and weight 1 (``-0.0`` reads as ``+0.0``)."""
+    return dequant_combine(torch.zeros(int(n), dtype=torch.float32, device=codes.device), codes.reshape(1, -1),
+                           scales.reshape(1, -1), torch.ones(1, dtype=torch.float32, device=codes.device), int(bits))
 
 
 def segment_sum_rows(rows, inv, num_out: int, clip: float = 0.0, noise_std: float = 0.0,

@@ -655,3 +655,185 @@ def sparse_upload_check(idx: torch.Tensor, val: torch.Tensor, n: int, k: int) ->
     if bad.numel():
         j = int(bad[0]) + 1
         raise ValueError(f"sparse upload: idx is not strictly ascending at {j} ({int(i[j - 1])} then {int(i[j])})")
+
+
+# ---------------------------------------------------------------------------------------
+# Block-quantized uploads with error feedback (oracle of csrc/quant_delta.hip)
+# ---------------------------------------------------------------------------------------
+QUANT_GROUP = 256  # coordinates per scale block
+
+
+def quant_levels(bits: int) -> int:
+    """``Q = 2^(bits - 1) - 1``: codes run over ``[-Q, Q]`` (127 at 8 bits, 7 at 4)."""
+    return (1 << (int(bits) - 1)) - 1
+
+
+def quant_sizes(n: int, bits: int) -> Tuple[int, int]:
+    """``(bytes of codes, scale blocks)`` of ``n`` coordinates."""
+    return (int(n) * int(bits) + 7) // 8, (int(n) + QUANT_GROUP - 1) // QUANT_GROUP
+
+
+def _canonical_nan() -> torch.Tensor:
+    return torch.tensor([0x7FC00000], dtype=torch.int32).view(torch.float32)[0]
+
+
+def quantize_delta_check(local: torch.Tensor, global_: torch.Tensor, residual: torch.Tensor, bits: int) -> None:
+    """The argument checks of ``fedrec_quant::quantize_delta``, with its messages."""
+    op = "fedrec_quant::quantize_delta"
+    _check_vec(local, op, "local")
+    _check_vec(global_, op, "global")
+    _check_vec(residual, op, "residual")
+    n = local.numel()
+    if not (global_.numel() == n and residual.numel() == n):
+        raise RuntimeError(f"{op}: local, global and residual must have one length (got {n}, {global_.numel()}, "
+                           f"{residual.numel()})")
+    if not (1 <= n < 2 ** 31):
+        raise RuntimeError(f"{op}: 1 <= n < 2^31 (got n {n})")
+    if bits not in (8, 4):
+        raise RuntimeError(f"{op}: bits must be 8 or 4 (got {bits})")
+    if not (local.device == residual.device and global_.device == residual.device):
+        raise RuntimeError(f"{op}: local, global and residual must be on one device")
+    if _overlaps(residual, local) or _overlaps(residual, global_):
+        raise RuntimeError(f"{op}: residual must not overlap local or global")
+
+
+def pack_codes(q: torch.Tensor, bits: int) -> torch.Tensor:
+    """Integer codes ``q [n]`` -> uint8 ``[ceil(n bits / 8)]``: at 8 bits byte ``i`` is ``q[i]`` as
+    two's-complement int8; at 4 bits byte ``j`` holds coordinate ``2 j`` in its low nibble and ``2 j + 1``
+    in its high nibble, each 4-bit two's complement, the padding nibble of an odd ``n`` zero."""
+    q = q.to(torch.int64)
+    if bits == 8:
+        return (q & 0xFF).to(torch.uint8)
+    nib = q & 0xF
+    if nib.numel() & 1:
+        nib = torch.cat([nib, nib.new_zeros(1)])
+    return (nib[0::2] | (nib[1::2] << 4)).to(torch.uint8)
+
+
+def unpack_codes(codes: torch.Tensor, bits: int, n: int) -> torch.Tensor:
+    """The inverse of :func:`pack_codes` over the last dimension -> int64 ``[..., n]``; every byte decodes
+    (``0x80`` is -128, the nibble ``0x8`` is -8)."""
+    c = codes.to(torch.int64)
+    if bits == 8:
+        return (((c & 0xFF) ^ 0x80) - 0x80)[..., :n]
+    nib = torch.stack([c & 0xF, (c >> 4) & 0xF], -1).reshape(*c.shape[:-1], -1)
+    return ((nib ^ 0x8) - 0x8)[..., :n]
+
+
+def quantize_delta(local: torch.Tensor, global_: torch.Tensor, residual: torch.Tensor, bits: int, seed: int,
+                   offset: int):
+    """Stochastic block quantisation with error feedback -> ``(codes uint8 [ceil(n bits / 8)], scales fp32
+    [ceil(n / 256)])``; ``residual`` is updated in place.
+
+    ``a = (local - global_) + residual`` (one fp32 subtraction, one fp32 addition).  Per block of 256
+    coordinates ``amax`` is the float whose bits are ``max(bits(a) & 0x7fffffff)``.  A block with an inf
+    or a NaN gets the canonical NaN as its scale, zero codes and a ``+0.0`` residual.  Otherwise ``s =
+    amax / Q`` (``Q = 2^(bits - 1) - 1``); ``s < 2^-126`` makes a zero block (scale ``+0.0``, zero codes,
+    ``residual = a``).  On a live block ``x = a / s``, ``f = floor(x)``, ``p = x - f``; the code rounds up
+    iff ``float(word >> 8) < p * 2^24`` with ``word`` component ``i & 3`` of ``philox4x32(seed, offset,
+    i >> 2)``; ``q = clamp(f + up, -Q, Q)`` (``fl(amax / fl(amax / Q))`` can exceed ``Q``); ``residual =
+    a - float(q) * s``, product and difference rounded separately.  Codes are packed as
+    :func:`pack_codes` does."""
+    bits = int(bits)
+    quantize_delta_check(local, global_, residual, bits)
+    n, G, Q = local.numel(), QUANT_GROUP, quant_levels(bits)
+    nb = (n + G - 1) // G
+    a = (local - global_) + residual
+    keys = F.pad(magnitude_keys(a), (0, nb * G - n)).view(nb, G)
+    amax_key = keys.max(1).values
+    amax = amax_key.view(torch.float32)
+    nonfinite = amax_key >= 0x7F800000
+    s = amax / torch.full_like(amax, float(Q))
+    live = ~nonfinite & (s >= 2.0 ** -126)
+    zero = torch.zeros((), dtype=torch.float32)
+    scales = torch.where(nonfinite, _canonical_nan(), torch.where(live, s, zero))
+    el = lambda t: t.repeat_interleave(G)[:n]  # noqa: E731  (per block -> per coordinate)
+    s_e, live_e = el(torch.where(live, s, torch.ones_like(s))), el(live)
+    x = a / s_e
+    f = torch.floor(x)
+    p = x - f
+    word = philox4x32(seed, offset, torch.arange((n + 3) // 4)).reshape(-1)[:n]
+    up = (word >> 8).to(torch.float32) < p * 16777216.0
+    q = torch.clamp(f + up.to(torch.float32), -float(Q), float(Q))
+    d = q * s_e
+    r = a - d
+    residual.copy_(torch.where(live_e, r, torch.where(el(nonfinite), zero, a)))
+    qi = torch.where(live_e, q, zero).to(torch.int64)
+    return pack_codes(qi, bits), scales
+
+
+def dequant_combine_check(base: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, weights: torch.Tensor,
+                          bits: int) -> None:
+    """The argument checks of ``fedrec_quant::dequant_combine``, with its messages."""
+    op = "fedrec_quant::dequant_combine"
+    _check_vec(base, op, "base")
+    if codes.dtype != torch.uint8:
+        raise RuntimeError(f"{op}: codes must be uint8")
+    if scales.dtype != torch.float32:
+        raise RuntimeError(f"{op}: scales must be fp32")
+    if not (codes.dim() == 2 and scales.dim() == 2):
+        raise RuntimeError(f"{op}: codes [W, nbytes] and scales [W, nb]")
+    if not (codes.is_contiguous() and scales.is_contiguous()):
+        raise RuntimeError(f"{op}: codes and scales must be contiguous")
+    _check_vec(weights, op, "weights")
+    n, W = base.numel(), codes.shape[0]
+    if not (1 <= n < 2 ** 31):
+        raise RuntimeError(f"{op}: 1 <= n < 2^31 (got n {n})")
+    if bits not in (8, 4):
+        raise RuntimeError(f"{op}: bits must be 8 or 4 (got {bits})")
+    if not (1 <= W <= 65536 and weights.numel() == W and scales.shape[0] == W):
+        raise RuntimeError(f"{op}: 1 <= W <= 65536, scales [W, nb] and weights [W] (got W {W}, scales "
+                           f"{scales.shape[0]}, weights {weights.numel()})")
+    nbytes, nb = quant_sizes(n, bits)
+    if not (codes.shape[1] == nbytes and scales.shape[1] == nb):
+        raise RuntimeError(f"{op}: n {n} at {bits} bits takes codes [W, {nbytes}] and scales [W, {nb}] (got "
+                           f"{codes.shape[1]}, {scales.shape[1]})")
+    if not (codes.device == base.device and scales.device == base.device and weights.device == base.device):
+        raise RuntimeError(f"{op}: base, codes, scales and weights must be on one device")
+
+
+def dequant_combine(base: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, weights: torch.Tensor,
+                    bits: int) -> torch.Tensor:
+    """``W`` quantised deltas applied to ``base [n]`` -> ``out [n]`` fp32.  ``codes [W, ceil(n bits / 8)]``
+    uint8, ``scales [W, ceil(n / 256)]`` fp32, ``weights [W]``.  ``acc`` starts at ``+0.0``; for ``c = 0 ..
+    W - 1`` in that order ``acc[i] += weights[c] * (float(q[c, i]) * scales[c, i / 256])`` (three
+    separately rounded operations); ``wsum`` is the sequential fp32 sum of the weights from ``+0.0``;
+    ``out = base + acc / wsum``.  Codes are taken as they decode (-128 and -8 included); rejecting a bad
+    upload is the caller's check (:func:`quant_upload_check`)."""
+    bits = int(bits)
+    dequant_combine_check(base, codes, scales, weights, bits)
+    n = base.numel()
+    acc = torch.zeros_like(base)
+    ws = torch.zeros((), dtype=torch.float32)
+    for c in range(codes.shape[0]):
+        q = unpack_codes(codes[c], bits, n).to(torch.float32)
+        acc = acc + weights[c] * (q * scales[c].repeat_interleave(QUANT_GROUP)[:n])
+        ws = ws + weights[c]
+    return base + acc / ws
+
+
+def dequantize(codes: torch.Tensor, scales: torch.Tensor, bits: int, n: int) -> torch.Tensor:
+    """One upload's delta ``d [n]``: :func:`dequant_combine` with ``W = 1``, a zero base and weight 1
+    (``-0.0`` reads as ``+0.0``)."""
+    return dequant_combine(torch.zeros(int(n), dtype=torch.float32, device=codes.device), codes.reshape(1, -1),
+                           scales.reshape(1, -1), torch.ones(1, dtype=torch.float32, device=codes.device), bits)
+
+
+def quant_upload_check(codes: torch.Tensor, scales: torch.Tensor, n: int, bits: int) -> None:
+    """A quantised upload as :func:`quantize_delta` makes it: ``codes`` uint8 ``[ceil(n bits / 8)]``,
+    ``scales`` fp32 ``[ceil(n / 256)]``, every scale finite and not below ``+0.0`` (``-0.0`` is below it).
+    Raises ``ValueError`` naming the first violation."""
+    nbytes, nb = quant_sizes(n, bits)
+    if codes.dtype != torch.uint8:
+        raise ValueError(f"quantized upload: codes must be uint8 (got {codes.dtype})")
+    if scales.dtype != torch.float32:
+        raise ValueError(f"quantized upload: scales must be fp32 (got {scales.dtype})")
+    if codes.dim() != 1 or codes.numel() != nbytes:
+        raise ValueError(f"quantized upload: codes must have length {nbytes} (got shape {tuple(codes.shape)})")
+    if scales.dim() != 1 or scales.numel() != nb:
+        raise ValueError(f"quantized upload: scales must have length {nb} (got shape {tuple(scales.shape)})")
+    sb = scales.contiguous().view(torch.int32)
+    bad = ((sb < 0) | (sb >= 0x7F800000)).nonzero()
+    if bad.numel():
+        j = int(bad[0])
+        raise ValueError(f"quantized upload: scales[{j}] = {float(scales[j])} is not a finite value >= +0.0")

@@ -25,6 +25,11 @@ fraction of its round delta and keep the rest as a residual for the next round (
 sparsification with error feedback); both star aggregations scatter the sparse lists onto the
 round's global model, and the records gain ``upload_bytes`` / ``dense_bytes``.
 
+``cfg.upload_bits`` (parallel/quantize.py) makes a star client upload its round delta (or, with
+``upload_topk``, the selected values) as stochastic 8- or 4-bit codes with one scale per 256
+coordinates, the quantisation error kept in the same residual; both star aggregations dequantise and
+combine in client order.
+
 All modes write ``snapshot.pt`` in the reference layout (rank 0 / coordinator, atomic) and
 JSONL metrics with the reference's metric names.
 """
@@ -49,6 +54,7 @@ from ..parallel import secagg
 from ..parallel.collcheck import CHECK
 from ..parallel.control import ControlPlane, Heartbeat, encode_tensor
 from ..parallel.robust import RobustRule
+from ..parallel.quantize import Quantizer
 from ..parallel.sparsify import Sparsifier
 from ..parallel.dist import (DistContext, data_ipc, make_bucket_reducer, make_grad_allreduce, make_secure_grad_allreduce,
                              selfcheck)
@@ -246,6 +252,7 @@ class ServerStep:
 def run_grad_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
     RobustRule.from_cfg(cfg, "grad_avg")  # (an active rule is rejected here)
     Sparsifier.from_cfg(cfg, "grad_avg")  # (and sparsified uploads: star only)
+    Quantizer.from_cfg(cfg, "grad_avg")  # (and quantised ones)
     selfcheck(ctx, log=obs.log)
     shard = load_client_shard(cfg, ctx)
     model = build_model(cfg, ctx.device)
@@ -291,6 +298,7 @@ def run_grad_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
 def run_param_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
     rule = RobustRule.from_cfg(cfg, "param_avg")
     Sparsifier.from_cfg(cfg, "param_avg")  # (an active sparsifier is rejected here: star only)
+    Quantizer.from_cfg(cfg, "param_avg")  # (and an active quantizer)
     selfcheck(ctx, log=obs.log)
     shard = load_client_shard(cfg, ctx)
     model = build_model(cfg, ctx.device)
@@ -390,8 +398,9 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
     fault = FaultInjector("client", k)
     rule = RobustRule.from_cfg(cfg, "fedavg_star")
     sparse = Sparsifier.from_cfg(cfg, "fedavg_star")
-    # what top-k sparsification has not sent yet (error feedback); zero at the start
-    residual = torch.zeros_like(model.flat.flat, dtype=torch.float32) if sparse.active else None
+    quant = Quantizer.from_cfg(cfg, "fedavg_star")
+    # what top-k sparsification / quantisation has not sent yet (error feedback); zero at the start
+    residual = torch.zeros_like(model.flat.flat, dtype=torch.float32) if sparse.active or quant.active else None
     agg = _aggregation(cfg, ctx)
     if rule.active and agg == "allreduce":
         rule.trim_for(ctx.num_clients)
@@ -417,7 +426,7 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
         info = ckpt.load_client_state(csnap, model, residual)
         eng.load_state(info["engine"])
         obs.log(f"[client {k}] resumed {csnap} (round {info['round']}, Adam step {model.flat.step})")
-        if sparse.active and not info.get("residual_restored"):
+        if residual is not None and not info.get("residual_restored"):
             obs.log(f"[client {k}] {csnap} holds no upload residual of {residual.numel()} elements: resuming with a "
                     "zero residual")
     beat = Heartbeat(cp, f"client{k}", cfg.heartbeat_s)
@@ -466,7 +475,7 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
         _receive_global(cp, r, model, ctx, full, bcast)
         _backbone_synced(model, full, before)
         # the round's global model
-        theta_g = model.flat.flat.detach().clone() if secure is not None or sparse.active else None
+        theta_g = model.flat.flat.detach().clone() if secure is not None or residual is not None else None
         eng.ensure_cache()  # after the broadcast every client is here: the collective build point
         eng.sigma = _maybe_dp(cfg, eng)
         eng.epoch = 0
@@ -491,7 +500,23 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
             ckpt.save_state_dict(os.path.join(_artifact_dir(cfg), sub, "model.pt"), model)
         beat(force=True)
         fault.before_upload(r, up)
-        if sparse.active:
+        if quant.active:
+            qup = quant.compress(up, theta_g.float(), residual, k, r)
+            if not quant.finite(qup):
+                # sent as it is (the coordinator rejects it); nothing of it may come back next round
+                residual.zero_()
+            blob = encode_tensor(quant.pack(qup))
+            meta.update({"upload_bytes": len(blob)})
+            if agg == "allreduce":
+                # the clients gather each other's uploads and every one of them combines the same stack
+                w = float(len(shard.train)) if cfg.weighted_fedavg else 1.0
+                new = quant.combine(theta_g.float(), *quant.gather(qup, w, ctx.data_group, ctx.num_clients, up.numel()))
+                if k == 0:
+                    cp.put_tensor(f"r{r}/avg", new.cpu())
+            else:
+                cp.set(f"r{r}/up/{k}", blob)
+            cp.put_json(f"r{r}/meta/{k}", meta)
+        elif sparse.active:
             idx, val = sparse.compress(up, theta_g.float(), residual)
             if not bool(torch.isfinite(val).all()):
                 # sent as it is (the coordinator rejects it); nothing of it may come back next round
@@ -587,6 +612,7 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
     server = ServerStep.from_cfg(cfg)  # off by default: the plain mean
     rule = RobustRule.from_cfg(cfg, "fedavg_star")
     sparse = Sparsifier.from_cfg(cfg, "fedavg_star")
+    quant = Quantizer.from_cfg(cfg, "fedavg_star")
     start_round = 0
     if cfg.snapshot_path and os.path.exists(cfg.snapshot_path):
         info = ckpt.load_snapshot(cfg.snapshot_path, model)
@@ -625,18 +651,26 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
                 try:
                     t = cp.get_tensor(key)
                     meta = cp.get_json(f"r{r}/meta/{k}", 30.0)
-                    if sparse.active:  # (idx, val); a malformed list drops the client like a corrupt blob
+                    if quant.active:  # a malformed upload or a non-finite scale drops the client like a corrupt blob
+                        t = quant.unpack(t, n_flat)
+                    elif sparse.active:  # (idx, val); a malformed list drops the client like a corrupt blob
                         t = sparse.unpack(t, n_flat, sparse.k_for(n_flat))
                 except Exception as e:  # corrupt blob / missing meta -> drop this client
                     obs.log(f"[server] round {r}: dropping client {k}: {e}")
                     continue
-                if not cfg.secagg.enabled and not torch.isfinite(t[1] if sparse.active else t).all():
+                if quant.active:
+                    pass  # (unpack has checked every scale)
+                elif not cfg.secagg.enabled and not torch.isfinite(t[1] if sparse.active else t).all():
                     obs.log(f"[server] round {r}: client {k} sent non-finite parameters; rejected")
                     continue
                 ups.append(t)
                 metas.append(meta)
                 accepted.append(k)
-                if sparse.active:
+                if quant.active:
+                    if cfg.round_artifacts:  # that client's model as far as its upload tells
+                        ckpt.atomic_save(ckpt.flat_to_state_dict(model, quant.received(model.flat.flat.detach().float(), t)),
+                                         os.path.join(_artifact_dir(cfg), f"received_model_{k}.pt"))
+                elif sparse.active:
                     if cfg.round_artifacts:  # that client's model as far as its upload tells
                         ckpt.atomic_save(ckpt.flat_to_state_dict(model, sparse.scatter(model.flat.flat, *t)),
                                          os.path.join(_artifact_dir(cfg), f"received_model_{k}.pt"))
@@ -655,6 +689,8 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
                 if new is None:
                     obs.log(f"[server] round {r}: a client's update is non-finite; the global model is kept")
                     new = model.flat.flat.detach().clone()
+            elif quant.active:
+                new = quant.combine(model.flat.flat.detach().float(), ups, weights)
             elif sparse.active:
                 new = sparse.combine(model.flat.flat.detach().float(), [u[0] for u in ups], [u[1] for u in ups],
                                      weights)
@@ -680,7 +716,9 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
             by = dict(zip(accepted, rule.record(dropped, new.numel(), len(accepted))["dropped_share"]))
             rec.update({"robust_agg": rule.kind, "robust_trim": rule.trim_for(len(accepted)),
                         "dropped_share": [by.get(k) for k in range(W)]})
-        if sparse.active:
+        if quant.active:
+            rec.update(quant.record(new.numel(), [int(m.get("upload_bytes", 0)) for m in metas]))
+        elif sparse.active:
             rec.update(sparse.record(new.numel(), [int(m.get("upload_bytes", 0)) for m in metas]))
         for key in ("training_loss", "validation_loss", "valid_auc", "valid_mrr", "val_ndcg@5", "val_ndcg@10",
                     "train_s", "valid_s"):
