@@ -207,15 +207,29 @@ Tensor4 head_wgrad_g(const at::Tensor& table, const OptTensor& ids, int64_t T, c
 }
 
 // ---- additive-attention pooling (additive_pool.hip) --------------------------------------------
+// x [n, T, D], e [n, T, Q] of one dtype (bf16 or fp32), w2 [Q] fp32: the kernels index all three by
+// x's n, T and e's Q, so a mismatch reads out of bounds.  One message per rule; the device checks
+// come after every shape check (they do not depend on the shapes)
+void pool_args(const char* op, const at::Tensor& x, const at::Tensor& e, const at::Tensor& w2) {
+  TORCH_CHECK(x.dim() == 3 && e.dim() == 3 && x.scalar_type() == e.scalar_type() &&
+                  (x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kFloat),
+              op, ": x [n, T, D] and e [n, T, Q] of one dtype, bf16 or fp32");
+  TORCH_CHECK(e.size(0) == x.size(0) && e.size(1) == x.size(1), op, ": e must share x's [n, T] (got e [", e.size(0),
+              ", ", e.size(1), "], x [", x.size(0), ", ", x.size(1), "])");
+  TORCH_CHECK(w2.scalar_type() == at::kFloat && w2.is_contiguous() && w2.numel() == e.size(2), op,
+              ": w2 must be contiguous fp32 of Q = ", e.size(2), " elements (got ", w2.numel(), ")");
+  TORCH_CHECK(x.is_contiguous() && e.is_contiguous(), op, ": x and e must be contiguous");
+}
+
 Tensor2 additive_pool_fwd(const at::Tensor& x, const at::Tensor& e, const at::Tensor& w2, const at::Tensor& b2,
                           const OptTensor& keep) {
-  check_dev(x, "x");
-  check_dev(e, "e");
-  TORCH_CHECK(x.dim() == 3 && e.dim() == 3 && x.scalar_type() == e.scalar_type(), "fedrec::additive_pool_fwd");
+  const char* op = "fedrec::additive_pool_fwd";
+  pool_args(op, x, e, w2);
+  TORCH_CHECK(b2.scalar_type() == at::kFloat && b2.numel() == 1, op, ": b2 must be fp32 of one element");
+  TORCH_CHECK(x.is_cuda() && e.is_cuda() && w2.is_cuda() && b2.is_cuda(), op, ": x, e, w2 and b2 must be device tensors");
   const c10::DeviceGuard g(x.device());
   const int64_t n = x.size(0), T = x.size(1), D = x.size(2), Q = e.size(2);
   const bool bf = x.scalar_type() == at::kBFloat16;
-  TORCH_CHECK(bf || x.scalar_type() == at::kFloat, "fedrec::additive_pool_fwd: dtype");
   auto out = at::empty({n, D}, x.options().dtype(at::kFloat));
   auto alpha = at::empty({n, T}, x.options().dtype(at::kFloat));
   check_rc(fr_additive_pool_fwd(x.data_ptr(), e.data_ptr(), w2.data_ptr<float>(), b2.data_ptr<float>(),
@@ -227,12 +241,17 @@ Tensor2 additive_pool_fwd(const at::Tensor& x, const at::Tensor& e, const at::Te
 
 Tensor5 additive_pool_bwd(const at::Tensor& x, const at::Tensor& e, const at::Tensor& alpha, const at::Tensor& w2,
                           const at::Tensor& g, bool want_dx) {
-  check_dev(x, "x");
-  check_dev(e, "e");
-  check_dev(alpha, "alpha");
-  check_dev(g, "g");
-  const c10::DeviceGuard dg(x.device());
+  const char* op = "fedrec::additive_pool_bwd";
+  pool_args(op, x, e, w2);
   const int64_t n = x.size(0), T = x.size(1), D = x.size(2), Q = e.size(2);
+  TORCH_CHECK(alpha.scalar_type() == at::kFloat && alpha.dim() == 2 && alpha.size(0) == n && alpha.size(1) == T &&
+                  alpha.is_contiguous(),
+              op, ": alpha must be contiguous fp32 [n, T] = [", n, ", ", T, "]");
+  TORCH_CHECK(g.scalar_type() == at::kFloat && g.dim() == 2 && g.size(0) == n && g.size(1) == D && g.is_contiguous(), op,
+              ": g must be contiguous fp32 [n, D] = [", n, ", ", D, "]");
+  TORCH_CHECK(x.is_cuda() && e.is_cuda() && alpha.is_cuda() && w2.is_cuda() && g.is_cuda(), op,
+              ": x, e, alpha, w2 and g must be device tensors");
+  const c10::DeviceGuard dg(x.device());
   const bool bf = x.scalar_type() == at::kBFloat16;
   auto fopt = x.options().dtype(at::kFloat);
   at::Tensor dx = want_dx ? at::empty({n, T, D}, fopt) : at::empty({0}, fopt);
@@ -247,6 +266,10 @@ Tensor5 additive_pool_bwd(const at::Tensor& x, const at::Tensor& e, const at::Te
                                       g.data_ptr<float>(), want_dx ? dx.data_ptr<float>() : nullptr, dpre.data_ptr(),
                                       dw2p, db2p, dsump, (int)n, (int)T, (int)D, (int)Q, (int)R, bf, cur_stream());
   TORCH_CHECK(rc <= 0, "fedrec::additive_pool_bwd: kernel launch rejected the arguments (code ", rc, ")");
+  if (n == 0) {  // nothing was launched, the partial row is unwritten: the sums are zero, no dsum
+    auto zeros = at::zeros({Q + 1}, fopt);
+    return {dx, dpre, zeros.narrow(0, 0, Q), zeros.narrow(0, Q, 1), at::empty({0}, fopt)};
+  }
   // the partial rows -> sums, one deterministic colsum launch (dw2, db2 and, from the text
   // kernel, the dpre column sums)
   auto sums = at::empty({2 * Q + 1}, fopt);
@@ -306,4 +329,11 @@ TORCH_LIBRARY_FRAGMENT(fedrec, m) {
   m.def("additive_pool_fwd(Tensor x, Tensor e, Tensor w2, Tensor b2, Tensor? keep=None) -> (Tensor, Tensor)", on_gpu(&additive_pool_fwd));
   m.def("additive_pool_bwd(Tensor x, Tensor e, Tensor alpha, Tensor w2, Tensor g, bool want_dx) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", on_gpu(&additive_pool_bwd));
   m.def("upool_bwd_da(Tensor x, Tensor e, Tensor alpha, Tensor w2, Tensor g, bool bf16_out=False) -> (Tensor, Tensor, Tensor, Tensor)", on_gpu(&upool_bwd_da));
+}
+
+// the pool ops take host tensors too: they reach the argument checks and fail the device check last
+// (there is no host kernel; ops.additive_pool_* sends host tensors to the torch oracle before it gets here)
+TORCH_LIBRARY_IMPL(fedrec, CPU, m) {
+  m.impl("additive_pool_fwd", &additive_pool_fwd);
+  m.impl("additive_pool_bwd", &additive_pool_bwd);
 }

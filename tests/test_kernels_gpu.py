@@ -138,7 +138,8 @@ def test_title_attention_launch_variants(dev, waves, n, T):
 @pytest.mark.parametrize("dtype,D,Q", [(torch.bfloat16, 768, 384), (torch.float32, 400, 200), (torch.bfloat16, 64, 32),
                                        (torch.bfloat16, 512, 256)])
 def test_additive_pool(dev, dtype, D, Q):
-    # per element, masked, eps-dominated and fused forms: tests/test_user_oracle_gpu.py
+    # per element, masked, eps-dominated and fused forms: tests/test_user_oracle_gpu.py (fp32),
+    # tests/test_text_pool_oracle_gpu.py (bf16)
     n, T = 23, 50
     x = torch.randn(n, T, D, device=dev).to(dtype)
     e = torch.tanh(torch.randn(n, T, Q, device=dev)).to(dtype)

@@ -132,6 +132,8 @@ product per term, on magnitudes (``sum_t da_t`` cancels to ``(1 - sum alpha) sum
     tol_dw2_q = sum_{n,t} (E_da_t + (T + 4 n + 3) u Mda_t) |e_tq| + TINY
     tol_db2   = sum_{n,t} (E_da_t + (T + 4 n + 3) u Mda_t) + TINY
 
+(The bf16 text-head forms take the same bounds on their bf16 operands: ``tests/text_pool_oracle.py``.)
+
 ================================================================================================
 3. Score + CE.  Per impression b, candidate c, label column 0::
 
