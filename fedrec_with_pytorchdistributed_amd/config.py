@@ -157,8 +157,12 @@ class FedRecConfig:
     # clients: "trimmed_mean" drops the robust_trim lowest and highest values, "median" the
     # (W - 1) // 2 on each side (ops.trimmed_mean; parallel/robust.py).  PA and both star
     # aggregations; unweighted, and the server must see the individual updates
-    robust_agg: str = "none"  # none | trimmed_mean | median
+    # "multi_krum" (Blanchard et al. 2017) ranks whole vectors instead: robust_trim is f, the assumed
+    # number of Byzantine clients (W >= 2 f + 3); each client is scored by its squared distances to its
+    # W - f - 2 nearest peers and the robust_keep best are averaged (0: W - f; 1: plain Krum)
+    robust_agg: str = "none"  # none | trimmed_mean | median | multi_krum
     robust_trim: int = 1
+    robust_keep: int = 0
     # star clients upload only the ceil(upload_topk * n) largest-magnitude coordinates of their round
     # delta and keep the rest as a residual added to the next round's delta (top-k sparsification
     # with error feedback; ops.topk_delta / ops.sparse_combine, parallel/sparsify.py).  0 = dense

@@ -195,6 +195,13 @@ int fr_mmr_rerank(const float* table, const int* ids, const float* rel, int* ids
 // ---- robust_agg.hip --------------------------------------------------------------------------
 int fr_trimmed_mean(const float* stack, float* out, long long* dropped, int W, long n, int trim, hipStream_t s);
 
+// ---- krum.hip --------------------------------------------------------------------------------
+long fr_krum_gram_ws(int W, long n);  // scratch of fr_krum_gram in floats
+int fr_krum_gram(const float* stack, const float* center, float* part, double* G, int W, long n, int max_blocks,
+                 hipStream_t s);
+int fr_krum_select(const double* G, int* selected, float* scores, int W, int f, int m, hipStream_t s);
+int fr_krum_selected_mean(const float* stack, const int* selected, float* out, int W, long n, hipStream_t s);
+
 // ---- sparse_delta.hip ------------------------------------------------------------------------
 long fr_topk_delta_ws(long n);  // workspace of fr_topk_delta in 32-bit words
 int fr_topk_delta(const float* local, const float* global, float* residual, int* idx, float* val, unsigned* ws, long n,

@@ -34,6 +34,10 @@ mmr_rerank            (beyond the reference)       mmr_rerank.hip: a pool's rows
 trimmed_mean          (beyond the reference)       robust_agg.hip: W <= 32 clients' values of a
                                                    coordinate sorted in registers (compile-time
                                                    network), trimmed mean / median + dropped counts
+krum_gram /           (beyond the reference)       krum.hip: the Gram matrix of the W centred rows in one
+krum_select /                                      register-direct pass on fp32 MFMA (one register is
+krum_mean                                          both operands), fixed-order chunk partials; Krum
+                                                   scores and picks in one wave; the picked rows' mean
 topk_delta /          (beyond the reference)       sparse_delta.hip: exact magnitude top-k of one long
 sparse_combine                                     row by radix select (no sort, no host sync) with
                                                    the error-feedback residual; W sparse lists
@@ -303,6 +307,43 @@ def trimmed_mean(stack, trim: int):
         native.require_for(stack)
         return tuple(torch.ops.fedrec_agg.trimmed_mean(stack, int(trim)))
     return ref.trimmed_mean(stack, int(trim))
+
+
+def krum_gram(stack, center, max_blocks: int = 0):
+    """``G = Y Y^T`` fp64 ``[W, W]`` of the centred rows ``Y = stack - center`` (``stack [W, n]`` fp32
+    contiguous, ``W <= 32``; ``center [n]`` fp32, for multi-Krum the coordinate-wise median).  The
+    squared distance of two clients is ``G_ii + G_jj - 2 G_ij``.  The device kernel reads every stack
+    element once, subtracts in registers, accumulates chunks of 1024 coordinates on the fp32 matrix
+    cores and adds the chunks in fp64 in a fixed order: ``G`` is symmetric and bitwise independent of
+    the grid (``max_blocks > 0`` caps it), and a NaN or inf of client ``c`` stays in row and column
+    ``c`` (csrc/krum.hip).  The host path: :func:`ops.reference.krum_gram`."""
+    if _dev(stack):
+        native.require_for(stack)
+        return torch.ops.fedrec_krum.centered_gram(stack, center, int(max_blocks))
+    return ref.krum_gram(stack, center, int(max_blocks))
+
+
+def krum_select(G, f: int, m: int):
+    """Krum scores and the multi-Krum pick from a Gram matrix -> ``(selected [W] int32 0 / 1, scores [W]
+    fp32)``: a client's score is the sum of its ``W - f - 2`` smallest squared distances, the ``m``
+    lowest ``(score, client index)`` are selected; non-finite distances rank highest.  ``W >= 2 f + 3``,
+    ``1 <= m <= W - f``.  One wave on the device, nothing returns to the host (csrc/krum.hip).  The
+    exact contract: :func:`ops.reference.krum_select`."""
+    if _dev(G):
+        native.require_for(G)
+        return tuple(torch.ops.fedrec_krum.select(G, int(f), int(m)))
+    return ref.krum_select(G, int(f), int(m))
+
+
+def krum_mean(stack, selected):
+    """The mean of the rows of ``stack [W, n]`` with ``selected [W] != 0`` (int32, on the stack's device):
+    fp32 adds in client order, one division; only the selected rows are read.  With every client
+    selected it is ``trimmed_mean(stack, 0)`` bit for bit (csrc/krum.hip).  The exact contract:
+    :func:`ops.reference.krum_mean`."""
+    if _dev(stack):
+        native.require_for(stack)
+        return torch.ops.fedrec_krum.selected_mean(stack, selected)
+    return ref.krum_mean(stack, selected)
 
 
 def topk_delta(local, global_, residual, k: int):

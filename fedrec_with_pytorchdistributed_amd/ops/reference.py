@@ -532,6 +532,121 @@ def trimmed_mean(stack: torch.Tensor, trim: int, acc_dtype: Optional[torch.dtype
 
 
 # ---------------------------------------------------------------------------------------
+# Multi-Krum aggregation (oracle of csrc/krum.hip)
+# ---------------------------------------------------------------------------------------
+def _krum_stack_check(stack: torch.Tensor, op: str) -> None:
+    if stack.dtype != torch.float32:
+        raise RuntimeError(f"{op}: stack must be fp32")
+    if stack.dim() != 2:
+        raise RuntimeError(f"{op}: stack [W, n] (got {stack.dim()} dims)")
+    if not stack.is_contiguous():
+        raise RuntimeError(f"{op}: stack must be contiguous")
+    W, n = stack.shape
+    if not (1 <= W <= 32 and n >= 1):
+        raise RuntimeError(f"{op}: 1 <= W <= 32, n >= 1 (got W {W}, n {n})")
+
+
+def krum_gram_check(stack: torch.Tensor, center: torch.Tensor, max_blocks: int = 0) -> None:
+    """The argument checks of ``fedrec_krum::centered_gram``, with its messages."""
+    op = "fedrec_krum::centered_gram"
+    _krum_stack_check(stack, op)
+    n = stack.shape[1]
+    if center.dtype != torch.float32:
+        raise RuntimeError(f"{op}: center must be fp32")
+    if not (center.dim() == 1 and center.numel() == n):
+        raise RuntimeError(f"{op}: center [n] (got {center.numel()} elements, n {n})")
+    if not center.is_contiguous():
+        raise RuntimeError(f"{op}: center must be contiguous")
+    if not (0 <= max_blocks < 2 ** 31):
+        raise RuntimeError(f"{op}: max_blocks >= 0 (got {max_blocks})")
+    if stack.device != center.device:
+        raise RuntimeError(f"{op}: stack and center must be on one device")
+
+
+def krum_select_check(G: torch.Tensor, f: int, m: int) -> None:
+    """The argument checks of ``fedrec_krum::select``, with its messages."""
+    op = "fedrec_krum::select"
+    if G.dtype != torch.float64:
+        raise RuntimeError(f"{op}: G must be fp64")
+    if not (G.dim() == 2 and G.shape[0] == G.shape[1]):
+        raise RuntimeError(f"{op}: G [W, W]")
+    if not G.is_contiguous():
+        raise RuntimeError(f"{op}: G must be contiguous")
+    W = G.shape[0]
+    if not (1 <= W <= 32):
+        raise RuntimeError(f"{op}: 1 <= W <= 32 (got W {W})")
+    if not (f >= 0 and W >= 2 * f + 3):
+        raise RuntimeError(f"{op}: f >= 0 and W >= 2 f + 3 (got f {f}, W {W})")
+    if not (1 <= m <= W - f):
+        raise RuntimeError(f"{op}: 1 <= m <= W - f (got m {m}, W {W}, f {f})")
+
+
+def krum_mean_check(stack: torch.Tensor, selected: torch.Tensor) -> None:
+    """The argument checks of ``fedrec_krum::selected_mean``, with its messages."""
+    op = "fedrec_krum::selected_mean"
+    _krum_stack_check(stack, op)
+    W = stack.shape[0]
+    if selected.dtype != torch.int32:
+        raise RuntimeError(f"{op}: selected must be int32")
+    if not (selected.dim() == 1 and selected.numel() == W):
+        raise RuntimeError(f"{op}: selected [W] (got {selected.numel()} elements, W {W})")
+    if not selected.is_contiguous():
+        raise RuntimeError(f"{op}: selected must be contiguous")
+    if stack.device != selected.device:
+        raise RuntimeError(f"{op}: stack and selected must be on one device")
+
+
+def krum_gram(stack: torch.Tensor, center: torch.Tensor, max_blocks: int = 0, chunk: int = 1 << 20) -> torch.Tensor:
+    """``G = Y Y^T`` fp64 ``[W, W]`` of the centred rows ``Y = stack - center``: the subtraction is one
+    fp32 operation per element (as the device kernel's), products and sums run in fp64.  Distances
+    ``G_ii + G_jj - 2 G_ij`` do not depend on ``center``; taking it near the rows (the coordinate-wise
+    median) keeps them from cancelling.  At most ``chunk`` columns are centred at a time."""
+    krum_gram_check(stack, center, int(max_blocks))
+    W, n = stack.shape
+    G = torch.zeros(W, W, dtype=torch.float64)
+    for s in range(0, n, chunk):
+        y = (stack[:, s:s + chunk] - center[s:s + chunk]).double()
+        G += y @ y.t()
+    return G
+
+
+def krum_select(G: torch.Tensor, f: int, m: int):
+    """Krum scores (Blanchard et al. 2017) from a Gram matrix -> ``(selected [W] int32, scores [W] fp32)``.
+    ``d_cj = max((G_cc + G_jj) - 2 G_cj, 0)`` in fp64, rounded to fp32, ``+inf`` where the fp64 value is
+    not finite; ``score_c`` is the sum of the ``W - f - 2`` smallest ``d_cj`` over ``j != c``, added in
+    ascending order in fp32 (a non-finite distance, hence score, ranks highest); the ``m`` clients with
+    the lowest ``(score, client index)`` get ``selected = 1``.  ``f >= 0``, ``W >= 2 f + 3``, ``1 <= m <= W -
+    f``; ``m = 1`` is plain Krum."""
+    f, m = int(f), int(m)
+    krum_select_check(G, f, m)
+    W = G.shape[0]
+    g = G.diagonal()
+    t = (g[:, None] + g[None, :]) - 2.0 * G
+    inf = torch.full((), float("inf"), dtype=torch.float32)
+    d = torch.where(torch.isfinite(t), t.clamp_min(0.0).float(), inf)
+    off = ~torch.eye(W, dtype=torch.bool)
+    v = torch.sort(d[off].view(W, W - 1), dim=1).values
+    scores = v[:, 0].clone()
+    for r in range(1, W - f - 2):
+        scores = scores + v[:, r]
+    order = torch.sort(scores, stable=True).indices[:m]  # stable: ties go to the lower client
+    selected = torch.zeros(W, dtype=torch.int32)
+    selected[order] = 1
+    return selected, scores
+
+
+def krum_mean(stack: torch.Tensor, selected: torch.Tensor) -> torch.Tensor:
+    """The mean of the rows with ``selected != 0``: added in CLIENT order in fp32, left to right from the
+    first selected row, then one division by their count (NaN when there is none)."""
+    krum_mean_check(stack, selected)
+    rows = torch.nonzero(selected).reshape(-1).tolist()
+    acc = stack[rows[0]].clone() if rows else torch.zeros(stack.shape[1])
+    for c in rows[1:]:
+        acc = acc + stack[c]
+    return acc / torch.full((1,), float(len(rows)), dtype=torch.float32).expand_as(acc)
+
+
+# ---------------------------------------------------------------------------------------
 # Top-k sparsified uploads with error feedback (oracle of csrc/sparse_delta.hip)
 # ---------------------------------------------------------------------------------------
 def _overlaps(a: torch.Tensor, b: torch.Tensor) -> bool:

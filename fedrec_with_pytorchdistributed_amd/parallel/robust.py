@@ -9,6 +9,15 @@ the drivers all-gather where the mean all-reduced (:meth:`RobustRule.gather_comb
 uploads on the coordinator.  The arithmetic is :func:`ops.trimmed_mean` -- the HIP kernel on device
 stacks, the torch oracle on the host -- so every client that combines the same stack holds the same
 bits.
+
+``multi_krum`` (Blanchard et al. 2017) judges a client by its whole vector instead: a sign-flipped,
+scaled or colluding update lies inside the honest spread at every single coordinate and still far from
+everybody as a vector.  Each client is scored by the sum of its squared distances to its ``W - f - 2``
+nearest peers (``f = robust_trim``, the assumed number of Byzantine clients; ``W >= 2 f + 3``), the
+``robust_keep`` best-scored clients (0: ``W - f``; 1: plain Krum) are kept and averaged.  The distances
+come from the Gram matrix of the rows centred on their coordinate-wise median (:func:`ops.krum_gram`,
+:func:`ops.krum_select`, :func:`ops.krum_mean`: csrc/krum.hip on the device); ``dropped[c]`` is ``n`` for
+a client that was not kept and 0 for one that was, so its ``dropped_share`` reads 1.0.
 """
 from __future__ import annotations
 
@@ -20,22 +29,24 @@ from torch._utils import _flatten_dense_tensors, _unflatten_dense_tensors
 from .. import ops
 from . import comm
 
-KINDS = ("none", "trimmed_mean", "median")
+KINDS = ("none", "trimmed_mean", "median", "multi_krum")
 
 
 class RobustRule:
-    def __init__(self, kind: str = "none", trim: int = 1):
+    def __init__(self, kind: str = "none", trim: int = 1, keep: int = 0):
         if kind not in KINDS:
             raise ValueError(f"robust_agg={kind!r}: expected {' | '.join(KINDS)}")
-        if kind == "trimmed_mean" and int(trim) < 0:
+        if kind in ("trimmed_mean", "multi_krum") and int(trim) < 0:
             raise ValueError(f"robust_trim={trim}: must be >= 0")
-        self.kind, self.trim = kind, int(trim)
+        if kind == "multi_krum" and int(keep) < 0:
+            raise ValueError(f"robust_keep={keep}: must be >= 0")
+        self.kind, self.trim, self.keep = kind, int(trim), int(keep)
 
     @classmethod
     def from_cfg(cls, cfg, driver: str = "") -> "RobustRule":
         """The rule of ``cfg``; an active rule is rejected where it cannot hold (``driver``: the
         federation driver that asks)."""
-        rule = cls(cfg.robust_agg, cfg.robust_trim)
+        rule = cls(cfg.robust_agg, cfg.robust_trim, cfg.robust_keep)
         if rule.active:
             if cfg.secagg.enabled:
                 raise ValueError(f"robust_agg={cfg.robust_agg} cannot be combined with secagg.enabled=1: under secure "
@@ -55,6 +66,12 @@ class RobustRule:
     def trim_for(self, W: int) -> int:
         """Values cut on each side among ``W`` clients; raises where the rule leaves nothing."""
         W = int(W)
+        if self.kind == "multi_krum":  # f Byzantine clients assumed; Krum's guarantee needs W >= 2 f + 3
+            if W < 2 * self.trim + 3 or not 0 <= self.keep <= W - self.trim:
+                raise ValueError(f"robust_agg=multi_krum with robust_trim={self.trim}, robust_keep={self.keep} needs "
+                                 f"at least {2 * self.trim + 3} clients and robust_keep <= clients - robust_trim "
+                                 f"(got {W})")
+            return self.trim
         trim = (W - 1) // 2 if self.kind == "median" else self.trim
         if W < 1 or 2 * trim >= W:
             raise ValueError(f"robust_agg={self.kind} with robust_trim={trim} needs more than {2 * trim} clients "
@@ -63,20 +80,53 @@ class RobustRule:
 
     def combine(self, stack: torch.Tensor):
         """``stack [W, n]`` fp32 -> ``(out [n], dropped [W] int64)`` on the stack's device."""
+        if self.kind == "multi_krum":
+            stack = stack.contiguous()
+            sel = self._krum_select(self._krum_gram(stack), stack.shape[0])
+            return ops.krum_mean(stack, sel), self._krum_dropped(sel, stack.shape[1])
         return ops.trimmed_mean(stack.contiguous(), self.trim_for(stack.shape[0]))
+
+    # multi-Krum in pieces (a multi-bucket gather adds the buckets' Gram matrices before it selects)
+    def _krum_gram(self, stack: torch.Tensor) -> torch.Tensor:
+        center, _ = ops.trimmed_mean(stack, (stack.shape[0] - 1) // 2)  # the coordinate-wise median
+        return ops.krum_gram(stack, center)
+
+    def _krum_select(self, G: torch.Tensor, W: int) -> torch.Tensor:
+        f = self.trim_for(W)
+        return ops.krum_select(G, f, self.keep or W - f)[0]
+
+    @staticmethod
+    def _krum_dropped(sel: torch.Tensor, n: int) -> torch.Tensor:
+        return (sel == 0).to(torch.int64) * int(n)
 
     def gather_combine_(self, tensors: Sequence[torch.Tensor], group, W: int,
                         bucket_bytes: int = comm.BUCKET_BYTES) -> torch.Tensor:
         """In place: every tensor becomes the rule's aggregate of the group's W copies of it.  The
         tensors travel flattened in ~28 MB buckets, one all-gather into a ``[W, len]`` stack each; at
-        most one bucket's stack exists at a time.  Returns the summed ``dropped [W]`` (int64, host)."""
+        most one bucket's stack exists at a time.  Returns the summed ``dropped [W]`` (int64, host).
+
+        ``multi_krum`` selects on whole vectors, so with more than one bucket it makes two passes and
+        moves every byte TWICE: pass 1 gathers each bucket and adds the buckets' Gram matrices in bucket
+        order (fp64, on the stack's device), one select follows, pass 2 gathers each bucket again and
+        averages the selected rows.  A single bucket is gathered once."""
         self.trim_for(W)  # before the first collective: every member raises alike
         dropped = torch.zeros(W, dtype=torch.int64)
-        for b in comm._buckets(list(tensors), bucket_bytes):
+        buckets = list(comm._buckets(list(tensors), bucket_bytes))
+        sel = None
+        if self.kind == "multi_krum" and len(buckets) > 1:
+            G = None
+            for b in buckets:
+                stack = comm.allgather_stack(_flatten_dense_tensors(b).float(), group, W)
+                g = self._krum_gram(stack)
+                del stack
+                G = g if G is None else G + g
+            sel = self._krum_select(G, W)
+        for b in buckets:
             one = len(b) == 1 and b[0].is_contiguous()
             flat = b[0].reshape(-1) if one else _flatten_dense_tensors(b)
             stack = comm.allgather_stack(flat.float(), group, W)
-            out, d = self.combine(stack)
+            out, d = (ops.krum_mean(stack, sel), self._krum_dropped(sel, stack.shape[1])) if sel is not None \
+                else self.combine(stack)
             del stack
             dropped += d.cpu()
             if one:
@@ -89,6 +139,6 @@ class RobustRule:
     def record(self, dropped, n: int, W: int) -> dict:
         """The keys a round / epoch record gains: ``dropped_share[c]`` is the fraction of the ``n``
         aggregated coordinates at which client ``c`` was cut (an honest client sits near
-        ``2 trim / W``, a poisoned one near 1)."""
+        ``2 trim / W``, a poisoned one near 1; under multi_krum 0 for a kept client, 1 for one left out)."""
         share: List[float] = [float(x) / max(int(n), 1) for x in dropped]
         return {"robust_agg": self.kind, "robust_trim": self.trim_for(W), "dropped_share": share}

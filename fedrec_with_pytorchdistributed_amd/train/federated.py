@@ -15,10 +15,10 @@
                    ``allreduce`` aggregation, the clients average among themselves over RCCL
                    and only the result goes to the coordinator.
 
-``cfg.robust_agg`` (``trimmed_mean`` | ``median``, parallel/robust.py) replaces the mean of
-``run_param_avg`` and of both star aggregations with the coordinate-wise robust rule: the
-all-reduces become all-gathers, and the records gain ``dropped_share`` (how often each client's
-value was cut).
+``cfg.robust_agg`` (``trimmed_mean`` | ``median`` | ``multi_krum``, parallel/robust.py) replaces the
+mean of ``run_param_avg`` and of both star aggregations with the robust rule -- coordinate-wise, or
+multi-Krum's choice of whole clients: the all-reduces become all-gathers, and the records gain
+``dropped_share`` (how often each client's value was cut).
 
 ``cfg.upload_topk`` (parallel/sparsify.py) makes a star client upload only the largest-magnitude
 fraction of its round delta and keep the rest as a residual for the next round (top-k
