@@ -12,20 +12,19 @@ quantised as a list of their own (scale blocks over the list positions); the ``k
 go back into the residual at the selected coordinates.  The upload is then ``4 k + 4 ceil(k / 256) + k B /
 8`` bytes, and the aggregation dequantises each list and scatters it as the sparse path does.
 
-The arithmetic is :func:`ops.quantize_delta` and :func:`ops.dequant_combine` -- the HIP kernels on device
-tensors, the torch oracles on the host, one bitwise contract -- so the coordinator (host) and clients
-that combine among themselves (device) hold the same bits.
+The arithmetic is :func:`ops.quantize_delta` and :func:`ops.dequant_combine`; :class:`Quantizer` is a codec of
+parallel/upload.py.
 """
 from __future__ import annotations
 
-from typing import List, NamedTuple, Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
 from .. import ops
 from ..ops import reference as ref
-from . import comm
 from .sparsify import Sparsifier
+from .upload import StarUpload
 
 
 class Upload(NamedTuple):
@@ -34,13 +33,14 @@ class Upload(NamedTuple):
     scales: torch.Tensor         # fp32 [ceil(m / 256)]
 
 
-class Quantizer:
+class Quantizer(StarUpload):  # (its payload: an Upload)
     def __init__(self, bits: int = 0, seed: int = 0, fraction: float = 0.0):
         if bits not in (0, 8, 4):
             raise ValueError(f"upload_bits={bits}: expected 0 (off), 8 or 4")
         self.bits = int(bits)
         self.seed = int(seed)
         self.sparse = Sparsifier(fraction)
+        self.options = {"upload_bits": self.bits, **({"upload_topk": self.sparse.fraction} if self.sparse.active else {})}
 
     @classmethod
     def from_cfg(cls, cfg, driver: str = "") -> "Quantizer":
@@ -91,6 +91,7 @@ class Quantizer:
 
     @staticmethod
     def finite(up: Upload) -> bool:
+        """(``unpack`` has checked every scale: what came through it is finite.)"""
         return bool(torch.isfinite(up.scales).all())
 
     @staticmethod
@@ -125,31 +126,18 @@ class Quantizer:
         ref.quant_upload_check(codes, scales, m, self.bits)
         return Upload(idx, codes, scales)
 
-    def gather(self, up: Upload, weight: float, group, W: int, n: int):
-        """All-gather the group's W packed uploads and weights -> ``(uploads, weights [W])``, every row
-        validated: each member ends up with the same tensors."""
-        mine = torch.cat([self.pack(up), torch.tensor([weight], dtype=torch.float32, device=up.codes.device).view(torch.int32)])
-        both = comm.allgather_stack(mine, group, W)
-        ups = []
-        for c in range(W):
-            try:
-                ups.append(self.unpack(both[c, :-1], n))
-            except ValueError as e:
-                raise RuntimeError(f"client {c}: {e}")
-        return ups, both[:, -1].contiguous().view(torch.float32)
-
     # ---- aggregation -------------------------------------------------------------------------
-    def combine(self, base: torch.Tensor, ups: Sequence[Upload], weights) -> torch.Tensor:
-        """``base + (sum_c w_c d_c) / sum_c w_c`` on ``base``'s device, in the order of ``ups``."""
+    def combine(self, base: torch.Tensor, ups: Sequence[Upload], weights):
+        """``(base + (sum_c w_c d_c) / sum_c w_c, None)`` on ``base``'s device, in the order of ``ups``."""
         w = weights if isinstance(weights, torch.Tensor) else torch.tensor([float(x) for x in weights], dtype=torch.float32,
                                                                               device=base.device)
         base = base.contiguous()
         if not self.sparse.active:
             return ops.dequant_combine(base, torch.stack([u.codes for u in ups]), torch.stack([u.scales for u in ups]),
-                                       w, self.bits)
+                                       w, self.bits), None
         k = self.m_for(base.numel())
         vals = [ops.dequantize(u.codes, u.scales, self.bits, k) for u in ups]
-        return ops.sparse_combine(base, torch.stack([u.idx for u in ups]).contiguous(), torch.stack(vals).contiguous(), w)
+        return ops.sparse_combine(base, torch.stack([u.idx for u in ups]).contiguous(), torch.stack(vals).contiguous(), w), None
 
     def received(self, base: torch.Tensor, up: Upload) -> torch.Tensor:
         """``base`` plus one client's dequantised delta (that client's model as the coordinator sees it)."""
@@ -157,11 +145,6 @@ class Quantizer:
         d = ops.dequantize(up.codes, up.scales, self.bits, m)
         if up.idx is None:
             return base.detach() + d
-        return Sparsifier.scatter(base, up.idx, d)
-
-    def record(self, n: int, upload_bytes: List[int]) -> dict:
-        """The keys a round record gains: the bytes the accepted clients sent against the dense form."""
-        rec = {"upload_bits": self.bits, "upload_bytes": int(sum(upload_bytes)), "dense_bytes": 4 * int(n) * len(upload_bytes)}
-        if self.sparse.active:
-            rec["upload_topk"] = self.sparse.fraction
-        return rec
+        out = base.detach().clone()
+        out[up.idx.long()] += d
+        return out

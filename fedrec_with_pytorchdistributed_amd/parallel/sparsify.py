@@ -4,22 +4,17 @@ A star client uploads its whole flat trainable buffer every round.  With ``uploa
 sends only the ``k = max(1, ceil(F n))`` largest-magnitude coordinates of ``(theta_k - theta_g) +
 residual`` and keeps the rest as its residual, which joins the next round's delta (Stich et al.
 2018; Lin et al. 2018): nothing is lost, only delayed, and the upload is ``8 k`` bytes instead of
-``4 n``.  The aggregate is ``theta_g + (sum_c w_c scatter(idx_c, val_c)) / sum_c w_c``.
-
-The arithmetic is :func:`ops.topk_delta` and :func:`ops.sparse_combine` -- the HIP kernels on
-device tensors, the torch oracles on the host, one bitwise contract -- so the coordinator (host)
-and clients that combine among themselves (device) hold the same bits.
+``4 n``.  The aggregate is ``theta_g + (sum_c w_c scatter(idx_c, val_c)) / sum_c w_c``
+(:func:`ops.topk_delta`, :func:`ops.sparse_combine`; the codec over this class: parallel/upload.py).
 """
 from __future__ import annotations
 
 import math
-from typing import List, Sequence, Tuple
 
 import torch
 
 from .. import ops
 from ..ops import reference as ref
-from . import comm
 
 
 class Sparsifier:
@@ -55,7 +50,6 @@ class Sparsifier:
         """Coordinates sent out of ``n``."""
         return min(int(n), max(1, int(math.ceil(self.fraction * int(n)))))
 
-    # ---- client ------------------------------------------------------------------------------
     def compress(self, local: torch.Tensor, theta_g: torch.Tensor, residual: torch.Tensor):
         """``(idx [k] int32 ascending, val [k] fp32)`` of this round; ``residual`` is updated in place."""
         return ops.topk_delta(local.contiguous(), theta_g.contiguous(), residual, self.k_for(local.numel()))
@@ -66,7 +60,7 @@ class Sparsifier:
         return torch.stack([idx, val.view(torch.int32)])
 
     @staticmethod
-    def unpack(blob: torch.Tensor, n: int, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    def unpack(blob: torch.Tensor, n: int, k: int) -> tuple[torch.Tensor, torch.Tensor]:
         """``(idx, val)`` of a packed upload, validated (:func:`ops.reference.sparse_upload_check`);
         ``ValueError`` names what is wrong with it."""
         if blob.dtype != torch.int32 or blob.dim() != 2 or blob.shape[0] != 2:
@@ -75,40 +69,3 @@ class Sparsifier:
         idx, val = blob[0].contiguous(), blob[1].contiguous().view(torch.float32)
         ref.sparse_upload_check(idx, val, n, k)
         return idx, val
-
-    def gather(self, idx: torch.Tensor, val: torch.Tensor, weight: float, group, W: int, n: int):
-        """All-gather the group's W lists and weights -> ``(idx [W, k], val [W, k], weights [W])``, every
-        list validated: each member ends up with the same three tensors."""
-        k = idx.numel()
-        mine = torch.cat([self.pack(idx, val).reshape(-1),
-                          torch.tensor([weight], dtype=torch.float32, device=idx.device).view(torch.int32)])
-        both = comm.allgather_stack(mine, group, W)
-        lists = both[:, :2 * k].reshape(W, 2, k)
-        for c in range(W):
-            try:
-                self.unpack(lists[c], n, k)
-            except ValueError as e:
-                raise RuntimeError(f"client {c}: {e}")
-        return (lists[:, 0].contiguous(), lists[:, 1].contiguous().view(torch.float32),
-                both[:, 2 * k].contiguous().view(torch.float32))
-
-    # ---- aggregation -------------------------------------------------------------------------
-    @staticmethod
-    def combine(base: torch.Tensor, idxs: Sequence[torch.Tensor], vals: Sequence[torch.Tensor],
-                weights: Sequence[float]) -> torch.Tensor:
-        """``base + (sum_c w_c scatter(idx_c, val_c)) / sum_c w_c`` on ``base``'s device."""
-        w = torch.tensor([float(x) for x in weights], dtype=torch.float32, device=base.device)
-        return ops.sparse_combine(base.contiguous(), torch.stack(list(idxs)).contiguous(),
-                                  torch.stack(list(vals)).contiguous(), w)
-
-    @staticmethod
-    def scatter(base: torch.Tensor, idx: torch.Tensor, val: torch.Tensor) -> torch.Tensor:
-        """``base`` plus one client's sparse delta (that client's model as the coordinator sees it)."""
-        out = base.detach().clone()
-        out[idx.long()] += val
-        return out
-
-    def record(self, n: int, upload_bytes: List[int]) -> dict:
-        """The keys a round record gains: the bytes the accepted clients sent against the dense form."""
-        return {"upload_topk": self.fraction, "upload_bytes": int(sum(upload_bytes)),
-                "dense_bytes": 4 * int(n) * len(upload_bytes)}

@@ -20,15 +20,11 @@ mean of ``run_param_avg`` and of both star aggregations with the robust rule -- 
 multi-Krum's choice of whole clients: the all-reduces become all-gathers, and the records gain
 ``dropped_share`` (how often each client's value was cut).
 
-``cfg.upload_topk`` (parallel/sparsify.py) makes a star client upload only the largest-magnitude
-fraction of its round delta and keep the rest as a residual for the next round (top-k
-sparsification with error feedback); both star aggregations scatter the sparse lists onto the
-round's global model, and the records gain ``upload_bytes`` / ``dense_bytes``.
-
-``cfg.upload_bits`` (parallel/quantize.py) makes a star client upload its round delta (or, with
-``upload_topk``, the selected values) as stochastic 8- or 4-bit codes with one scale per 256
-coordinates, the quantisation error kept in the same residual; both star aggregations dequantise and
-combine in client order.
+What a star client uploads is the run's codec (parallel/upload.py, ``StarUpload.from_cfg``): the dense model, with
+``cfg.upload_topk`` the largest-magnitude fraction of its round delta, with ``cfg.upload_bits`` stochastic 8- or 4-bit
+codes of it; what was not sent stays in a residual for the next round (error feedback), and the records gain
+``upload_bytes`` / ``dense_bytes``.  A round's tail is secure aggregation or the codec, among the clients
+(``combine_among``) or through the coordinator (``pack`` -> store -> ``unpack`` / ``combine``).
 
 All modes write ``snapshot.pt`` in the reference layout (rank 0 / coordinator, atomic) and
 JSONL metrics with the reference's metric names.
@@ -48,14 +44,10 @@ from ..config import FedRecConfig
 from ..data.shard import Shard
 from ..data.synthetic import SynthSpec, SyntheticCorpus
 from ..models.fedrec_model import FedRecModel
-from .. import ops
-from ..parallel import catalog, comm
-from ..parallel import secagg
+from ..parallel import catalog, comm, secagg
 from ..parallel.collcheck import CHECK
 from ..parallel.control import ControlPlane, Heartbeat, encode_tensor
-from ..parallel.robust import RobustRule
-from ..parallel.quantize import Quantizer
-from ..parallel.sparsify import Sparsifier
+from ..parallel.upload import StarUpload
 from ..parallel.dist import (DistContext, data_ipc, make_bucket_reducer, make_grad_allreduce, make_secure_grad_allreduce,
                              selfcheck)
 from ..privacy.rdp import calibrate_client_sigma
@@ -250,9 +242,7 @@ class ServerStep:
 
 # ---------------------------------------------------------------------------------------
 def run_grad_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
-    RobustRule.from_cfg(cfg, "grad_avg")  # (an active rule is rejected here)
-    Sparsifier.from_cfg(cfg, "grad_avg")  # (and sparsified uploads: star only)
-    Quantizer.from_cfg(cfg, "grad_avg")  # (and quantised ones)
+    StarUpload.from_cfg(cfg, "grad_avg")  # (an active rule, sparsified or quantised uploads are rejected here)
     selfcheck(ctx, log=obs.log)
     shard = load_client_shard(cfg, ctx)
     model = build_model(cfg, ctx.device)
@@ -296,9 +286,7 @@ def run_grad_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
 
 
 def run_param_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
-    rule = RobustRule.from_cfg(cfg, "param_avg")
-    Sparsifier.from_cfg(cfg, "param_avg")  # (an active sparsifier is rejected here: star only)
-    Quantizer.from_cfg(cfg, "param_avg")  # (and an active quantizer)
+    rule = StarUpload.from_cfg(cfg, "param_avg").rule  # (sparsified or quantised uploads are rejected here: star only)
     selfcheck(ctx, log=obs.log)
     shard = load_client_shard(cfg, ctx)
     model = build_model(cfg, ctx.device)
@@ -385,10 +373,6 @@ def _artifact_dir(cfg: FedRecConfig) -> str:
     return os.path.dirname(os.path.abspath(cfg.snapshot_path or "snapshot.pt"))
 
 
-def _client_upload_tensor(model: FedRecModel, cfg: FedRecConfig) -> torch.Tensor:
-    return model.flat.flat.detach().float()
-
-
 def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -> Dict:
     cp = ControlPlane.from_default(run_id, cfg.round_timeout_s)
     k = ctx.client_index
@@ -396,14 +380,12 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
     model = build_model(cfg, ctx.device)  # created ONCE: Adam moments persist across rounds
     eng = LocalEngine(cfg, model, shard, ctx.device, rank=ctx.rank, grad_allreduce=None)
     fault = FaultInjector("client", k)
-    rule = RobustRule.from_cfg(cfg, "fedavg_star")
-    sparse = Sparsifier.from_cfg(cfg, "fedavg_star")
-    quant = Quantizer.from_cfg(cfg, "fedavg_star")
+    codec = StarUpload.from_cfg(cfg, "fedavg_star")
     # what top-k sparsification / quantisation has not sent yet (error feedback); zero at the start
-    residual = torch.zeros_like(model.flat.flat, dtype=torch.float32) if sparse.active or quant.active else None
+    residual = torch.zeros_like(model.flat.flat, dtype=torch.float32) if codec.uses_residual else None
     agg = _aggregation(cfg, ctx)
-    if rule.active and agg == "allreduce":
-        rule.trim_for(ctx.num_clients)
+    if agg == "allreduce":
+        codec.check_clients(ctx.num_clients)  # an impossible rule fails before the first round
     full = cfg.sync == "full"
     writer = _metrics_writer(cfg, False)
     # secure aggregation: pairwise seeds by Diffie-Hellman over the control plane
@@ -494,72 +476,34 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
             t_valid += time.perf_counter() - t1
         meta = {"client": k, "n_train": len(shard.train), "train_s": t_train, "valid_s": t_valid,
                 **{m: float(v) for m, v in {**tr, **va}.items() if isinstance(v, (int, float))}}
-        up = _client_upload_tensor(model, cfg).clone()
+        up = model.flat.flat.detach().float().clone()
         if cfg.round_artifacts:  # client.py:288 torch.save(model.state_dict(), "model.pt")
             sub = "" if ctx.num_clients == 1 else f"client{k}"
             ckpt.save_state_dict(os.path.join(_artifact_dir(cfg), sub, "model.pt"), model)
         beat(force=True)
+        w = float(len(shard.train)) if cfg.weighted_fedavg else 1.0
         fault.before_upload(r, up)
-        if quant.active:
-            qup = quant.compress(up, theta_g.float(), residual, k, r)
-            if not quant.finite(qup):
-                # sent as it is (the coordinator rejects it); nothing of it may come back next round
-                residual.zero_()
-            blob = encode_tensor(quant.pack(qup))
-            meta.update({"upload_bytes": len(blob)})
-            if agg == "allreduce":
-                # the clients gather each other's uploads and every one of them combines the same stack
-                w = float(len(shard.train)) if cfg.weighted_fedavg else 1.0
-                new = quant.combine(theta_g.float(), *quant.gather(qup, w, ctx.data_group, ctx.num_clients, up.numel()))
-                if k == 0:
-                    cp.put_tensor(f"r{r}/avg", new.cpu())
-            else:
-                cp.set(f"r{r}/up/{k}", blob)
-            cp.put_json(f"r{r}/meta/{k}", meta)
-        elif sparse.active:
-            idx, val = sparse.compress(up, theta_g.float(), residual)
-            if not bool(torch.isfinite(val).all()):
-                # sent as it is (the coordinator rejects it); nothing of it may come back next round
-                residual.zero_()
-            blob = encode_tensor(sparse.pack(idx, val))
-            meta.update({"upload_k": int(idx.numel()), "upload_bytes": len(blob)})
-            if agg == "allreduce":
-                # the clients gather each other's lists and every one of them scatters the same W lists
-                w = float(len(shard.train)) if cfg.weighted_fedavg else 1.0
-                new = ops.sparse_combine(theta_g.float().contiguous(),
-                                         *sparse.gather(idx, val, w, ctx.data_group, ctx.num_clients, up.numel()))
-                if k == 0:
-                    cp.put_tensor(f"r{r}/avg", new.cpu())
-            else:
-                cp.set(f"r{r}/up/{k}", blob)
-            cp.put_json(f"r{r}/meta/{k}", meta)
-        elif agg == "allreduce" and rule.active:
-            # the clients gather each other's uploads and every one of them combines the same stack
-            dropped = rule.gather_combine_([up], ctx.data_group, ctx.num_clients)
-            if k == 0:
-                cp.put_tensor(f"r{r}/avg", up.cpu())
-                meta["dropped"] = [int(x) for x in dropped]
-            cp.put_json(f"r{r}/meta/{k}", meta)
-        elif agg == "allreduce":
-            w = float(len(shard.train)) if cfg.weighted_fedavg else 1.0
-            wt = torch.tensor([w], device=up.device, dtype=torch.float32)
-            up.mul_(wt)
-            ipc = data_ipc(ctx, cfg.collective_timeout_s) if ctx.device.type == "cuda" else None
-            comm.allreduce_([up, wt], ctx.data_group, ipc=ipc)
-            if ipc is not None:
-                ipc.check()
-            up.div_(wt)
-            if k == 0:
-                cp.put_tensor(f"r{r}/avg", up.cpu())
-            cp.put_json(f"r{r}/meta/{k}", meta)
+        if secure is not None:
+            # exact: the weighted delta on the grid the masked exponent histogram agrees
+            meta.update(secure.upload(r, up, theta_g, w))
         else:
-            if secure is not None:
-                # exact: the weighted delta on the grid the masked exponent histogram agrees
-                w = float(len(shard.train)) if cfg.weighted_fedavg else 1.0
-                meta.update(secure.upload(r, up, theta_g, w))
+            pay = codec.compress(up, theta_g, residual, k, r)
+            if codec.uses_residual and not codec.finite(pay):
+                # sent as it is (the coordinator rejects it); nothing of it may come back next round
+                residual.zero_()
+            if agg == "allreduce":
+                # the clients combine among themselves and every one of them ends up with the same bits
+                new, dropped = codec.combine_among(pay, w, ctx, theta_g, cfg.collective_timeout_s)
+                if k == 0:
+                    cp.put_tensor(f"r{r}/avg", new.cpu())
+                    if dropped is not None:
+                        meta["dropped"] = [int(x) for x in dropped]
+                meta.update(codec.meta(pay))
             else:
-                cp.put_tensor(f"r{r}/up/{k}", up.cpu())
-            cp.put_json(f"r{r}/meta/{k}", meta)
+                blob = encode_tensor(codec.pack(pay))
+                cp.set(f"r{r}/up/{k}", blob)
+                meta.update(codec.meta(pay, blob))
+        cp.put_json(f"r{r}/meta/{k}", meta)
         if csnap:
             # after the upload (off the round's critical path), EVERY round, and only what a
             # resume needs: trainable flat + Adam + RNG + engine counters (~14 MB, not the 270 MB
@@ -610,9 +554,7 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
     W = ctx.num_clients
     model = build_model(cfg, torch.device("cpu"))
     server = ServerStep.from_cfg(cfg)  # off by default: the plain mean
-    rule = RobustRule.from_cfg(cfg, "fedavg_star")
-    sparse = Sparsifier.from_cfg(cfg, "fedavg_star")
-    quant = Quantizer.from_cfg(cfg, "fedavg_star")
+    codec = StarUpload.from_cfg(cfg, "fedavg_star")  # (dense under secure aggregation: its uploads pass as they are)
     start_round = 0
     if cfg.snapshot_path and os.path.exists(cfg.snapshot_path):
         info = ckpt.load_snapshot(cfg.snapshot_path, model)
@@ -634,54 +576,39 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
         dead: List[int] = []
         dropped = None  # robust rule: how often each ACCEPTED client's value was cut
         if agg == "allreduce":
-            avg = cp.get_tensor(f"r{r}/avg", cfg.round_timeout_s)
+            new = cp.get_tensor(f"r{r}/avg", cfg.round_timeout_s)
             metas = [cp.get_json(f"r{r}/meta/{k}") for k in range(W)]
             accepted = list(range(W))
-            new = avg
-            if rule.active:
-                dropped = metas[0].get("dropped")
+            dropped = metas[0].get("dropped")
         else:
             keys = {k: f"r{r}/up/{k}" for k in range(W)}
             present, dead = cp.wait_uploads(keys, need, cfg.round_timeout_s, cfg.heartbeat_timeout_s,
                                             log=lambda m: obs.log(f"[server] round {r}: {m}"))
             ups, metas, accepted = [], [], []
-            n_flat = model.flat.flat.numel()
+            base = model.flat.flat.detach().float()
             for key in present:
                 k = int(key.rsplit("/", 1)[1])
-                try:
+                try:  # corrupt blob / missing meta / malformed upload -> drop this client
                     t = cp.get_tensor(key)
                     meta = cp.get_json(f"r{r}/meta/{k}", 30.0)
-                    if quant.active:  # a malformed upload or a non-finite scale drops the client like a corrupt blob
-                        t = quant.unpack(t, n_flat)
-                    elif sparse.active:  # (idx, val); a malformed list drops the client like a corrupt blob
-                        t = sparse.unpack(t, n_flat, sparse.k_for(n_flat))
-                except Exception as e:  # corrupt blob / missing meta -> drop this client
+                    t = codec.unpack(t, base.numel())
+                except Exception as e:
                     obs.log(f"[server] round {r}: dropping client {k}: {e}")
                     continue
-                if quant.active:
-                    pass  # (unpack has checked every scale)
-                elif not cfg.secagg.enabled and not torch.isfinite(t[1] if sparse.active else t).all():
-                    obs.log(f"[server] round {r}: client {k} sent non-finite parameters; rejected")
-                    continue
+                if not cfg.secagg.enabled:  # (a masked upload tells nothing of its client)
+                    if not codec.finite(t):
+                        obs.log(f"[server] round {r}: client {k} sent non-finite parameters; rejected")
+                        continue
+                    if cfg.round_artifacts:  # server.py:27 received_model_{k}.pt: that client's model as far as its upload tells
+                        ckpt.atomic_save(ckpt.flat_to_state_dict(model, codec.received(base, t)),
+                                         os.path.join(_artifact_dir(cfg), f"received_model_{k}.pt"))
                 ups.append(t)
                 metas.append(meta)
                 accepted.append(k)
-                if quant.active:
-                    if cfg.round_artifacts:  # that client's model as far as its upload tells
-                        ckpt.atomic_save(ckpt.flat_to_state_dict(model, quant.received(model.flat.flat.detach().float(), t)),
-                                         os.path.join(_artifact_dir(cfg), f"received_model_{k}.pt"))
-                elif sparse.active:
-                    if cfg.round_artifacts:  # that client's model as far as its upload tells
-                        ckpt.atomic_save(ckpt.flat_to_state_dict(model, sparse.scatter(model.flat.flat, *t)),
-                                         os.path.join(_artifact_dir(cfg), f"received_model_{k}.pt"))
-                elif cfg.round_artifacts and not cfg.secagg.enabled:  # server.py:27 received_model_{k}.pt
-                    ckpt.atomic_save(ckpt.flat_to_state_dict(model, t),
-                                     os.path.join(_artifact_dir(cfg), f"received_model_{k}.pt"))
             if cfg.secagg.enabled and len(accepted) != W:
                 raise RuntimeError(f"secure aggregation needs every client (got {len(accepted)}/{W})")
             if len(accepted) < need:
                 raise RuntimeError(f"round {r}: quorum not reached ({len(accepted)}/{W} < {need}); aborting")
-            weights = [float(m["n_train"]) if cfg.weighted_fedavg else 1.0 for m in metas]
             if cfg.secagg.enabled:
                 # the clients uploaded (w_k / sum w)(theta_k - theta_g) on the agreed grid: the
                 # unmasked sum IS the FedAvg update (secagg.StarSecureUpload)
@@ -689,22 +616,13 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
                 if new is None:
                     obs.log(f"[server] round {r}: a client's update is non-finite; the global model is kept")
                     new = model.flat.flat.detach().clone()
-            elif quant.active:
-                new = quant.combine(model.flat.flat.detach().float(), ups, weights)
-            elif sparse.active:
-                new = sparse.combine(model.flat.flat.detach().float(), [u[0] for u in ups], [u[1] for u in ups],
-                                     weights)
-            elif rule.active:
+            else:
                 try:
-                    rule.trim_for(len(ups))
+                    codec.check_clients(len(ups))
                 except ValueError as e:  # like a missed quorum: too few updates left to rank
                     raise RuntimeError(f"round {r}: {e} ({len(accepted)}/{W} accepted); aborting")
-                new, dropped = rule.combine(torch.stack([t.float() for t in ups]))
-            else:
-                acc = torch.zeros_like(ups[0], dtype=torch.float64)
-                for t, w in zip(ups, weights):
-                    acc += t.double() * w  # server.py:46-50 (unweighted unless weighted_fedavg)
-                new = (acc / sum(weights)).float()
+                weights = [float(m["n_train"]) if cfg.weighted_fedavg else 1.0 for m in metas]
+                new, dropped = codec.combine(base, ups, weights)
         last_accepted = list(accepted)
         with torch.no_grad():
             if server.active:  # FedAvgM / server learning rate / FedAdam on the round's mean (fp64)
@@ -712,14 +630,10 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
             model.flat.flat.copy_(new)
         dt = time.perf_counter() - t0
         rec = {"round": r, "clients_accepted": len(accepted), "clients": W, "clients_dead": dead, "round_s": dt}
-        if rule.active and dropped is not None:  # one share per client; a client not accepted has none
-            by = dict(zip(accepted, rule.record(dropped, new.numel(), len(accepted))["dropped_share"]))
-            rec.update({"robust_agg": rule.kind, "robust_trim": rule.trim_for(len(accepted)),
-                        "dropped_share": [by.get(k) for k in range(W)]})
-        if quant.active:
-            rec.update(quant.record(new.numel(), [int(m.get("upload_bytes", 0)) for m in metas]))
-        elif sparse.active:
-            rec.update(sparse.record(new.numel(), [int(m.get("upload_bytes", 0)) for m in metas]))
+        rec.update(codec.record(new.numel(), metas, dropped))
+        if "dropped_share" in rec:  # one share per client; a client not accepted has none
+            by = dict(zip(accepted, rec["dropped_share"]))
+            rec["dropped_share"] = [by.get(k) for k in range(W)]
         for key in ("training_loss", "validation_loss", "valid_auc", "valid_mrr", "val_ndcg@5", "val_ndcg@10",
                     "train_s", "valid_s"):
             vals = [m[key] for m in metas if key in m]
