@@ -159,8 +159,10 @@ class FedRecConfig:
     # aggregations; unweighted, and the server must see the individual updates
     # "multi_krum" (Blanchard et al. 2017) ranks whole vectors instead: robust_trim is f, the assumed
     # number of Byzantine clients (W >= 2 f + 3); each client is scored by its squared distances to its
-    # W - f - 2 nearest peers and the robust_keep best are averaged (0: W - f; 1: plain Krum)
-    robust_agg: str = "none"  # none | trimmed_mean | median | multi_krum
+    # W - f - 2 nearest peers and the robust_keep best are averaged (0: W - f; 1: plain Krum).
+    # "geomed" (RFA, Pillutla et al. 2022) is the geometric median of the clients' vectors: any W >= 1,
+    # nothing to guess (robust_trim and robust_keep are ignored), a soft weight per client
+    robust_agg: str = "none"  # none | trimmed_mean | median | multi_krum | geomed
     robust_trim: int = 1
     robust_keep: int = 0
     # star clients upload only the ceil(upload_topk * n) largest-magnitude coordinates of their round

@@ -202,6 +202,10 @@ int fr_krum_gram(const float* stack, const float* center, float* part, double* G
 int fr_krum_select(const double* G, int* selected, float* scores, int W, int f, int m, hipStream_t s);
 int fr_krum_selected_mean(const float* stack, const int* selected, float* out, int W, long n, hipStream_t s);
 
+// ---- geomed.hip ------------------------------------------------------------------------------
+int fr_geomed_weights(const double* G, double* a, float* dist, int W, hipStream_t s);
+int fr_geomed_combine(const float* stack, const double* a, float* out, int W, long n, hipStream_t s);
+
 // ---- sparse_delta.hip ------------------------------------------------------------------------
 long fr_topk_delta_ws(long n);  // workspace of fr_topk_delta in 32-bit words
 int fr_topk_delta(const float* local, const float* global, float* residual, int* idx, float* val, unsigned* ws, long n,

@@ -38,6 +38,10 @@ krum_gram /           (beyond the reference)       krum.hip: the Gram matrix of 
 krum_select /                                      register-direct pass on fp32 MFMA (one register is
 krum_mean                                          both operands), fixed-order chunk partials; Krum
                                                    scores and picks in one wave; the picked rows' mean
+geomed_weights /      (beyond the reference)       geomed.hip: Weiszfeld's geometric-median iteration on
+geomed_combine                                     the W x W Gram matrix in one wave (a row of G per lane
+                                                   in registers, v_readlane broadcasts); the weighted
+                                                   sum of the rows of non-zero weight
 topk_delta /          (beyond the reference)       sparse_delta.hip: exact magnitude top-k of one long
 sparse_combine                                     row by radix select (no sort, no host sync) with
                                                    the error-feedback residual; W sparse lists
@@ -344,6 +348,30 @@ def krum_mean(stack, selected):
         native.require_for(stack)
         return torch.ops.fedrec_krum.selected_mean(stack, selected)
     return ref.krum_mean(stack, selected)
+
+
+def geomed_weights(G):
+    """Weiszfeld weights of the geometric median from the centred Gram matrix ``G [W, W]`` fp64 (``W <= 32``,
+    :func:`krum_gram`) -> ``(a [W] fp64, dist [W] fp32)``: the aggregate is ``sum_c a_c x_c``, ``dist_c`` is
+    client ``c``'s distance to it.  Exactly 32 rounds on ``W`` numbers per client, never on the stack; a
+    client whose ``G_cc`` is not finite gets weight 0 and distance ``+inf``.  One wave on the device, a row of
+    ``G`` per lane in registers, nothing returns to the host (csrc/geomed.hip).  The exact contract:
+    :func:`ops.reference.geomed_weights`."""
+    if _dev(G):
+        native.require_for(G)
+        return tuple(torch.ops.fedrec_geomed.weights(G))
+    return ref.geomed_weights(G)
+
+
+def geomed_combine(stack, a):
+    """``sum_c fp32(a_c) x_c`` over the rows of ``stack [W, n]`` fp32 with a non-zero weight (``a [W]`` fp64 on
+    the stack's device), in client order, each product and sum rounded on its own in fp32: host and device
+    hold the same bits, and a row of weight zero is never read (csrc/geomed.hip).  The exact contract:
+    :func:`ops.reference.geomed_combine`."""
+    if _dev(stack):
+        native.require_for(stack)
+        return torch.ops.fedrec_geomed.combine(stack, a)
+    return ref.geomed_combine(stack, a)
 
 
 def topk_delta(local, global_, residual, k: int):

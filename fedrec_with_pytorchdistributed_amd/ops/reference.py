@@ -647,6 +647,98 @@ def krum_mean(stack: torch.Tensor, selected: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------
+# Geometric-median aggregation on the Gram matrix (oracle of csrc/geomed.hip)
+# ---------------------------------------------------------------------------------------
+GM_ITERS = 32  # Weiszfeld rounds, fixed: the device kernel and this oracle run one recurrence
+
+
+def geomed_weights_check(G: torch.Tensor) -> None:
+    """The argument checks of ``fedrec_geomed::weights``, with its messages."""
+    op = "fedrec_geomed::weights"
+    if G.dtype != torch.float64:
+        raise RuntimeError(f"{op}: G must be fp64")
+    if not (G.dim() == 2 and G.shape[0] == G.shape[1]):
+        raise RuntimeError(f"{op}: G [W, W]")
+    if not G.is_contiguous():
+        raise RuntimeError(f"{op}: G must be contiguous")
+    if not (1 <= G.shape[0] <= 32):
+        raise RuntimeError(f"{op}: 1 <= W <= 32 (got W {G.shape[0]})")
+
+
+def geomed_combine_check(stack: torch.Tensor, a: torch.Tensor) -> None:
+    """The argument checks of ``fedrec_geomed::combine``, with its messages."""
+    op = "fedrec_geomed::combine"
+    _krum_stack_check(stack, op)
+    W = stack.shape[0]
+    if a.dtype != torch.float64:
+        raise RuntimeError(f"{op}: a must be fp64")
+    if not (a.dim() == 1 and a.numel() == W):
+        raise RuntimeError(f"{op}: a [W] (got {a.numel()} elements, W {W})")
+    if not a.is_contiguous():
+        raise RuntimeError(f"{op}: a must be contiguous")
+    if stack.device != a.device:
+        raise RuntimeError(f"{op}: stack and a must be on one device")
+
+
+def geomed_weights(G: torch.Tensor, descending: bool = False):
+    """Weiszfeld's iteration for the geometric median of ``W`` rows, run on their centred Gram matrix
+    ``G [W, W]`` fp64 -> ``(a [W] fp64, dist [W] fp32)``: the aggregate is ``sum_c a_c x_c`` and ``dist_c`` is
+    client ``c``'s distance to it.  With ``z = center + sum_c a_c y_c``, ``||x_i - z||^2 = G_ii - 2 (G a)_i +
+    a^T G a``: no pass over the stack per round.
+
+    Client ``c`` is valid iff ``G_cc`` is finite; an invalid one gets ``a_c = 0`` and ``dist_c = +inf`` (no
+    valid client: every ``a_c`` is NaN).  ``nu2 = 1e-12 m + 1e-300`` smooths the weights, ``m`` the lower median
+    of the valid ``G_cc``.  From ``a`` uniform over the valid clients, exactly ``GM_ITERS`` rounds in fp64, each
+    product and sum rounded on its own: ``g_c = sum_j G_cj a_j`` over the valid ``j`` in ascending order (the
+    columns of invalid clients count as zeros), ``q = sum_c a_c g_c`` over the valid ``c`` ascending, ``d2_c =
+    max((G_cc - 2 g_c) + q, 0)``, ``w_c = 1 / sqrt(d2_c + nu2)``, ``a = w / sum_c w_c`` (ascending).
+    ``dist_c = fp32(sqrt(d2_c))`` of the last round.  ``descending`` runs the three sums from the highest
+    client down: the rounding probe of the tests."""
+    geomed_weights_check(G)
+    W = G.shape[0]
+    diag = G.diagonal().clone()
+    valid = torch.isfinite(diag)
+    nv = int(valid.sum())
+    if nv == 0:
+        return torch.full((W,), float("nan"), dtype=torch.float64), torch.full((W,), float("inf"))
+    nu2 = 1e-12 * float(torch.sort(diag[valid]).values[(nv - 1) // 2]) + 1e-300
+    zero = torch.zeros((), dtype=torch.float64)
+    Gm = torch.where(valid[None, :], G, zero)
+    a = torch.where(valid, torch.ones(W, dtype=torch.float64) / float(nv), zero)
+    order = range(W - 1, -1, -1) if descending else range(W)
+
+    def total(v):  # python floats are IEEE doubles
+        s, v = 0.0, v.tolist()
+        for c in order:
+            s = s + v[c]
+        return s
+
+    for _ in range(GM_ITERS):
+        g = torch.zeros(W, dtype=torch.float64)
+        for j in order:
+            g = g + Gm[:, j] * a[j]
+        q = total(torch.where(valid, a * g, zero))
+        d2 = ((diag - 2.0 * g) + q).clamp_min(0.0)
+        w = torch.where(valid, 1.0 / torch.sqrt(d2 + nu2), zero)
+        a = w / total(w)
+    return a, torch.where(valid, torch.sqrt(d2).float(), torch.full((W,), float("inf")))
+
+
+def geomed_combine(stack: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
+    """``out = sum_c a32_c x_c`` with ``a32 = fp32(a)``, over the clients with ``a32_c != 0`` in CLIENT order:
+    the first product initialises the sum, every product and every sum is rounded on its own in fp32.  A row
+    of weight zero is never read (a NaN or inf client under weight 0 cannot reach ``out``); a NaN weight makes
+    ``out`` NaN everywhere; all-zero weights leave zeros."""
+    geomed_combine_check(stack, a)
+    a32 = a.float()
+    rows = torch.nonzero(a32 != 0).reshape(-1).tolist()
+    acc = stack[rows[0]] * a32[rows[0]] if rows else torch.zeros(stack.shape[1])
+    for c in rows[1:]:
+        acc = acc + stack[c] * a32[c]
+    return acc
+
+
+# ---------------------------------------------------------------------------------------
 # Top-k sparsified uploads with error feedback (oracle of csrc/sparse_delta.hip)
 # ---------------------------------------------------------------------------------------
 def _overlaps(a: torch.Tensor, b: torch.Tensor) -> bool:

@@ -77,6 +77,10 @@ def allgather_stack(flat: torch.Tensor, group, W: int) -> torch.Tensor:
     """Every member's contiguous 1-D ``flat`` (the same length and dtype on each) -> ``[W, len]``, row
     ``c`` from the group's member ``c``."""
     CHECK.record("all_gather", flat, f"W={W}")
+    if flat.is_cuda and dist.get_backend(group) == "gloo":  # clients sharing a card: gloo moves host tensors
+        host = torch.empty(W * flat.numel(), dtype=flat.dtype)
+        dist.all_gather_into_tensor(host, flat.cpu(), group=group)
+        return host.to(flat.device).view(W, flat.numel())
     out = flat.new_empty(W * flat.numel())  # the concatenated form: every backend takes it
     dist.all_gather_into_tensor(out, flat, group=group)
     return out.view(W, flat.numel())

@@ -15,10 +15,11 @@
                    ``allreduce`` aggregation, the clients average among themselves over RCCL
                    and only the result goes to the coordinator.
 
-``cfg.robust_agg`` (``trimmed_mean`` | ``median`` | ``multi_krum``, parallel/robust.py) replaces the
-mean of ``run_param_avg`` and of both star aggregations with the robust rule -- coordinate-wise, or
-multi-Krum's choice of whole clients: the all-reduces become all-gathers, and the records gain
-``dropped_share`` (how often each client's value was cut).
+``cfg.robust_agg`` (``trimmed_mean`` | ``median`` | ``multi_krum`` | ``geomed``, parallel/robust.py) replaces the
+mean of ``run_param_avg`` and of both star aggregations with the robust rule -- coordinate-wise,
+multi-Krum's choice of whole clients, or the geometric median's soft weights: the all-reduces become
+all-gathers, and the records gain ``dropped_share`` (how often each client's value was cut) and, under
+``geomed``, ``agg_weight`` (each client's weight in the last aggregate).
 
 What a star client uploads is the run's codec (parallel/upload.py, ``StarUpload.from_cfg``): the dense model, with
 ``cfg.upload_topk`` the largest-magnitude fraction of its round delta, with ``cfg.upload_bits`` stochastic 8- or 4-bit
