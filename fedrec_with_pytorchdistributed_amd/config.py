@@ -78,6 +78,21 @@ class DPConfig:
 
 
 @dataclass
+class ClientDPConfig:
+    """Client-level (user-level) differential privacy on a star client's round update, DP-FedAvg (McMahan et
+    al. 2018; parallel/cdp.py): every client clips its delta to ``clip`` and adds its 1 / W share of Gaussian
+    noise of scale ``noise_multiplier * clip`` before anything leaves it.  Off by default."""
+
+    clip: float = 0.0  # L2 bound C on a client's round delta; 0 = off
+    noise_multiplier: Optional[float] = None  # z; 0 = clip only (epsilon reads inf)
+    epsilon: float = 0.0  # > 0 and no multiplier: z calibrated for (epsilon, delta) over global_rounds
+    delta: float = 1e-5
+    # 0: each client draws its Philox key from OS entropy at start and tells nobody; non-zero: a known key,
+    # for tests and reproduction only (noise anyone can regenerate is not noise)
+    seed: int = 0
+
+
+@dataclass
 class SecAggConfig:
     """Pairwise-mask secure aggregation (README.md:56,65 describes it; never implemented there)."""
 
@@ -191,6 +206,7 @@ class FedRecConfig:
 
     # --- privacy / secure aggregation --------------------------------------------------
     dp: DPConfig = field(default_factory=DPConfig)
+    cdp: ClientDPConfig = field(default_factory=ClientDPConfig)
     secagg: SecAggConfig = field(default_factory=SecAggConfig)
 
     # --- engine ------------------------------------------------------------------------

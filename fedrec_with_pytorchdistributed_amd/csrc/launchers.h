@@ -206,6 +206,13 @@ int fr_krum_selected_mean(const float* stack, const int* selected, float* out, i
 int fr_geomed_weights(const double* G, double* a, float* dist, int W, hipStream_t s);
 int fr_geomed_combine(const float* stack, const double* a, float* out, int W, long n, hipStream_t s);
 
+// ---- dp_clip.hip -----------------------------------------------------------------------------
+long fr_dp_sqnorm_ws(long n);  // scratch of fr_dp_delta_sqnorm in doubles
+int fr_dp_delta_sqnorm(const float* local, const float* base, double* part, void* state, long n, int max_blocks,
+                       hipStream_t s);
+int fr_dp_clip_noise(const float* local, const float* base, float* out, void* state, long n, double clip, float std,
+                     unsigned long long seed, unsigned long long offset, hipStream_t s);
+
 // ---- sparse_delta.hip ------------------------------------------------------------------------
 long fr_topk_delta_ws(long n);  // workspace of fr_topk_delta in 32-bit words
 int fr_topk_delta(const float* local, const float* global, float* residual, int* idx, float* val, unsigned* ws, long n,

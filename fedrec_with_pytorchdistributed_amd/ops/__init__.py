@@ -42,6 +42,10 @@ geomed_weights /      (beyond the reference)       geomed.hip: Weiszfeld's geome
 geomed_combine                                     the W x W Gram matrix in one wave (a row of G per lane
                                                    in registers, v_readlane broadcasts); the weighted
                                                    sum of the rows of non-zero weight
+dp_delta_sqnorm /     (beyond the reference)       dp_clip.hip: client-level DP on a round delta; its squared
+dp_clip_noise                                      norm in fp64 in a fixed order (register-direct, the next
+                                                   chunk's loads in flight), then clip + Philox Gaussian
+                                                   noise in one pass, the scale never leaving the device
 topk_delta /          (beyond the reference)       sparse_delta.hip: exact magnitude top-k of one long
 sparse_combine                                     row by radix select (no sort, no host sync) with
                                                    the error-feedback residual; W sparse lists
@@ -372,6 +376,33 @@ def geomed_combine(stack, a):
         native.require_for(stack)
         return torch.ops.fedrec_geomed.combine(stack, a)
     return ref.geomed_combine(stack, a)
+
+
+def dp_delta_sqnorm(local, base, max_blocks: int = 0):
+    """``|| local - base ||^2`` of a round delta (``local``, ``base`` ``[n]`` fp32 contiguous) in fp64 -> the 16-byte
+    privatisation state, int32 ``[4]`` on the inputs' device: ``sq`` (fp64), then the clip scale ``s`` (fp32) and
+    ``clipped`` (int32) that :func:`dp_clip_noise` fills in; ``ops.reference.dp_state_fields`` reads it.  One fp32
+    subtraction per coordinate, exact squares, a summation order that depends on ``n`` alone: host and device
+    hold the same bits whatever the grid (``max_blocks > 0`` caps it).  Nothing returns to the host
+    (csrc/dp_clip.hip).  The exact contract: :func:`ops.reference.dp_delta_sqnorm`."""
+    if _dev(local):
+        native.require_for(local)
+        return torch.ops.fedrec_dp.delta_sqnorm(local, base, int(max_blocks))
+    return ref.dp_delta_sqnorm(local, base, int(max_blocks))
+
+
+def dp_clip_noise(local, base, state, clip: float, std: float, seed: int, offset: int):
+    """``base + s (local - base) + std z`` -> ``out [n]`` fp32: the delta clipped to L2 norm ``clip`` (``s = min(1,
+    clip / sqrt(sq))`` from ``state`` of :func:`dp_delta_sqnorm`, taken in fp64 and rounded once) plus Gaussian
+    noise of scale ``std`` from Philox under the key ``(seed, offset)``.  An unclipped model passes through bit
+    for bit, a non-finite one as it is; ``std = 0`` draws nothing.  ``state`` gains ``s`` and ``clipped``.  ``sq``,
+    ``s``, ``clipped`` and the clipped part are one bitwise contract between host and device; the noise is not (the
+    device's ``logf`` / ``__sincosf`` are not torch's) and need not be: every client draws its own
+    (csrc/dp_clip.hip).  The exact contract: :func:`ops.reference.dp_clip_noise`."""
+    if _dev(local):
+        native.require_for(local)
+        return torch.ops.fedrec_dp.clip_noise(local, base, state, float(clip), float(std), int(seed), int(offset))
+    return ref.dp_clip_noise(local, base, state, float(clip), float(std), int(seed), int(offset))
 
 
 def topk_delta(local, global_, residual, k: int):

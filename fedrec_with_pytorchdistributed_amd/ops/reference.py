@@ -739,6 +739,123 @@ def geomed_combine(stack: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------
+# Client-level DP on a round delta: clip + noise (oracle of csrc/dp_clip.hip)
+# ---------------------------------------------------------------------------------------
+DP_L = 1024  # coordinates per chunk of the squared norm
+DP_SLOTS = 64  # partial sums of the finishing pass
+
+
+def _dp_pair_check(local: torch.Tensor, base: torch.Tensor, op: str) -> int:
+    if local.dtype != torch.float32 or base.dtype != torch.float32:
+        raise RuntimeError(f"{op}: local and base must be fp32")
+    if not (local.dim() == 1 and base.dim() == 1):
+        raise RuntimeError(f"{op}: local [n] and base [n] (got {local.dim()} and {base.dim()} dims)")
+    if not (local.is_contiguous() and base.is_contiguous()):
+        raise RuntimeError(f"{op}: local and base must be contiguous")
+    n = local.numel()
+    if base.numel() != n:
+        raise RuntimeError(f"{op}: local and base must have one length (got {n}, {base.numel()})")
+    if n < 1:
+        raise RuntimeError(f"{op}: n >= 1 (got n {n})")
+    if local.device != base.device:
+        raise RuntimeError(f"{op}: local and base must be on one device")
+    return n
+
+
+def dp_state_fields(state: torch.Tensor):
+    """``(sq fp64, s fp32, clipped int32)`` of a 16-byte privatisation state (one host read)."""
+    st = state.detach().cpu().contiguous()
+    return float(st.view(torch.float64)[0]), float(st.view(torch.float32)[2]), int(st[3])
+
+
+def dp_delta_sqnorm(local: torch.Tensor, base: torch.Tensor, max_blocks: int = 0, block: int = 1 << 20) -> torch.Tensor:
+    """``|| local - base ||^2`` in fp64 in the device kernel's order -> the state, int32 ``[4]``: bytes 0..7
+    ``sq`` (fp64), 8..11 the clip scale ``s`` (fp32) and 12..15 ``clipped`` (int32), both zero until
+    :func:`dp_clip_noise` fills them in.
+
+    ``d_k = local_k - base_k`` is one fp32 subtraction; its square is exact in fp64.  Chunk ``p`` covers ``[1024
+    p, 1024 (p + 1))``; lane ``l`` of 64 adds the 16 squares of the chunk's coordinate quads ``l, l + 64, l + 128, l +
+    192`` in ascending coordinate order from +0.0; the lane sums meet in an xor butterfly 32, 16, 8, 4, 2, 1;
+    slot ``t`` of 64 adds the chunk sums ``p = t, t + 64, ...`` ascending, then the slots add in order.  Coordinates
+    at and past ``n`` are zeros.  The order depends on ``n`` alone (``max_blocks`` caps the device grid and changes
+    nothing; ``block``, a multiple of 65,536, bounds this function's memory)."""
+    op = "fedrec_dp::delta_sqnorm"
+    n = _dp_pair_check(local, base, op)
+    if not (0 <= int(max_blocks) < 2 ** 31):
+        raise RuntimeError(f"{op}: max_blocks >= 0 (got {max_blocks})")
+    lanes = torch.arange(64)
+    slots = torch.zeros(DP_SLOTS, dtype=torch.float64)
+    for s0 in range(0, n, block):  # whole groups of 64 chunks: the slot order is kept across blocks
+        d = (local[s0:s0 + block] - base[s0:s0 + block]).double()
+        P = -(-d.numel() // DP_L)
+        sq = torch.zeros(P * DP_L, dtype=torch.float64)
+        sq[:d.numel()] = d * d
+        sq = sq.view(P, 4, 64, 4).permute(0, 2, 1, 3).reshape(P, 64, 16)
+        v = torch.zeros(P, 64, dtype=torch.float64)
+        for i in range(16):
+            v = v + sq[:, :, i]
+        for o in (32, 16, 8, 4, 2, 1):
+            v = v + v[:, lanes ^ o]
+        part = torch.zeros(-(-P // DP_SLOTS) * DP_SLOTS, dtype=torch.float64)  # x + 0.0 is x for a sum of squares
+        part[:P] = v[:, 0]
+        for row in part.view(-1, DP_SLOTS):
+            slots = slots + row
+    tot = 0.0 + float(slots[0])
+    for t in slots[1:].tolist():  # python floats are IEEE doubles
+        tot = tot + t
+    state = torch.zeros(4, dtype=torch.int32)
+    state.view(torch.float64)[0] = tot
+    return state
+
+
+def dp_normals(n: int, seed: int, offset: int) -> torch.Tensor:
+    """The fp32 standard normals of coordinates ``0 .. n - 1`` as ``common.h`` ``box_muller`` forms them: Philox
+    counter ``k >> 2`` under ``(seed, offset)``, component ``k & 3``; words (x, y) make components 0 and 1, (z, w)
+    2 and 3.  torch's ``log`` / ``sin`` / ``cos`` are not the device's ``logf`` / ``__sincosf``: the bits differ."""
+    w = philox4x32(seed, offset, torch.arange((n + 3) // 4))
+    u = ((w >> 8) + 1).to(torch.float32) * (1.0 / 16777216.0)
+    u1, u2 = u[:, 0::2], u[:, 1::2]
+    r = torch.sqrt(-2.0 * torch.log(u1))
+    ang = torch.tensor(6.283185307179586, dtype=torch.float32) * u2
+    return torch.stack([r * torch.cos(ang), r * torch.sin(ang)], -1).reshape(-1)[:n]
+
+
+def dp_clip_noise(local: torch.Tensor, base: torch.Tensor, state: torch.Tensor, clip: float, std: float, seed: int,
+                  offset: int) -> torch.Tensor:
+    """The round delta clipped to L2 norm ``clip`` on top of ``base``, plus Gaussian noise of scale ``std``;
+    ``state`` (of :func:`dp_delta_sqnorm` for the same pair) gains ``s`` and ``clipped`` in place.
+
+    ``s = fp32(min(1, clip / sqrt(sq)))``, root and division in IEEE fp64; ``s = 1`` where ``sq`` is 0 or not
+    finite.  ``p = local`` where ``s == 1`` (bit for bit), else ``base + s * (local - base)`` with every fp32
+    operation rounded on its own.  ``out = p`` when ``std == 0``, else ``p + fp32(std) * z`` with ``z`` of
+    :func:`dp_normals`.  ``clipped = (s < 1)``.  ``sq``, ``s``, ``clipped`` and ``p`` are bitwise the device's; the
+    noise is not (see :func:`dp_normals`), and need not be: every client draws its own."""
+    op = "fedrec_dp::clip_noise"
+    n = _dp_pair_check(local, base, op)
+    if not (state.dtype == torch.int32 and state.dim() == 1 and state.numel() == 4 and state.is_contiguous()):
+        raise RuntimeError(f"{op}: state must be the int32 [4] of delta_sqnorm")
+    clip, std = float(clip), float(std)
+    if not clip > 0.0:
+        raise RuntimeError(f"{op}: clip > 0 (got {clip})")
+    std32 = torch.tensor(std, dtype=torch.float32)
+    if not (std >= 0.0 and bool(torch.isfinite(std32))):
+        raise RuntimeError(f"{op}: 0 <= std < inf (got {std})")
+    if local.device != state.device:
+        raise RuntimeError(f"{op}: local, base and state must be on one device")
+    sq = float(state.view(torch.float64)[0])
+    s = torch.ones((), dtype=torch.float32)
+    if 0.0 < sq < math.inf:
+        r = clip / math.sqrt(sq)
+        if r < 1.0:
+            s = torch.tensor(r, dtype=torch.float64).float()  # one rounding
+    clipped = bool(s < 1)
+    state.view(torch.float32)[2] = s
+    state[3] = int(clipped)
+    p = base + s * (local - base) if clipped else local.clone()
+    return p + std32 * dp_normals(n, seed, offset) if std > 0.0 else p
+
+
+# ---------------------------------------------------------------------------------------
 # Top-k sparsified uploads with error feedback (oracle of csrc/sparse_delta.hip)
 # ---------------------------------------------------------------------------------------
 def _overlaps(a: torch.Tensor, b: torch.Tensor) -> bool:

@@ -49,6 +49,7 @@ from ..parallel import catalog, comm, secagg
 from ..parallel.collcheck import CHECK
 from ..parallel.control import ControlPlane, Heartbeat, encode_tensor
 from ..parallel.upload import StarUpload
+from ..parallel.cdp import ClientDP
 from ..parallel.dist import (DistContext, data_ipc, make_bucket_reducer, make_grad_allreduce, make_secure_grad_allreduce,
                              selfcheck)
 from ..privacy.rdp import calibrate_client_sigma
@@ -244,6 +245,7 @@ class ServerStep:
 # ---------------------------------------------------------------------------------------
 def run_grad_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
     StarUpload.from_cfg(cfg, "grad_avg")  # (an active rule, sparsified or quantised uploads are rejected here)
+    ClientDP.from_cfg(cfg, "grad_avg")  # (client-level DP as well: star only)
     selfcheck(ctx, log=obs.log)
     shard = load_client_shard(cfg, ctx)
     model = build_model(cfg, ctx.device)
@@ -288,6 +290,7 @@ def run_grad_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
 
 def run_param_avg(cfg: FedRecConfig, ctx: DistContext) -> Dict:
     rule = StarUpload.from_cfg(cfg, "param_avg").rule  # (sparsified or quantised uploads are rejected here: star only)
+    ClientDP.from_cfg(cfg, "param_avg")  # (client-level DP as well)
     selfcheck(ctx, log=obs.log)
     shard = load_client_shard(cfg, ctx)
     model = build_model(cfg, ctx.device)
@@ -382,6 +385,7 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
     eng = LocalEngine(cfg, model, shard, ctx.device, rank=ctx.rank, grad_allreduce=None)
     fault = FaultInjector("client", k)
     codec = StarUpload.from_cfg(cfg, "fedavg_star")
+    cdp = ClientDP.from_cfg(cfg, "fedavg_star", ctx.num_clients)  # client-level DP: clip + noise before the upload
     # what top-k sparsification / quantisation has not sent yet (error feedback); zero at the start
     residual = torch.zeros_like(model.flat.flat, dtype=torch.float32) if codec.uses_residual else None
     agg = _aggregation(cfg, ctx)
@@ -458,7 +462,8 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
         _receive_global(cp, r, model, ctx, full, bcast)
         _backbone_synced(model, full, before)
         # the round's global model
-        theta_g = model.flat.flat.detach().clone() if secure is not None or residual is not None else None
+        theta_g = (model.flat.flat.detach().clone() if secure is not None or residual is not None or cdp.active
+                   else None)
         eng.ensure_cache()  # after the broadcast every client is here: the collective build point
         eng.sigma = _maybe_dp(cfg, eng)
         eng.epoch = 0
@@ -478,6 +483,12 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
         meta = {"client": k, "n_train": len(shard.train), "train_s": t_train, "valid_s": t_valid,
                 **{m: float(v) for m, v in {**tr, **va}.items() if isinstance(v, (int, float))}}
         up = model.flat.flat.detach().float().clone()
+        if cdp.active:
+            # before the fault injector (a poisoned client does not clip itself) and before either tail: the
+            # secure upload and the codecs take the privatised model as they take any model.  What the clip
+            # saw is private: it goes to this client's own log and into no meta
+            up = cdp.privatize(up, theta_g, k, r)
+            obs.log(f"[client {k}] round {r}: cdp delta norm {cdp.last['delta_norm']:.4g}, scale {cdp.last['scale']:.4g}")
         if cfg.round_artifacts:  # client.py:288 torch.save(model.state_dict(), "model.pt")
             sub = "" if ctx.num_clients == 1 else f"client{k}"
             ckpt.save_state_dict(os.path.join(_artifact_dir(cfg), sub, "model.pt"), model)
@@ -556,10 +567,12 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
     model = build_model(cfg, torch.device("cpu"))
     server = ServerStep.from_cfg(cfg)  # off by default: the plain mean
     codec = StarUpload.from_cfg(cfg, "fedavg_star")  # (dense under secure aggregation: its uploads pass as they are)
+    cdp = ClientDP.from_cfg(cfg, "fedavg_star", W)  # here: the accountant of what the clients clipped and noised
     start_round = 0
     if cfg.snapshot_path and os.path.exists(cfg.snapshot_path):
         info = ckpt.load_snapshot(cfg.snapshot_path, model)
         server.load(info.get("server_opt"))
+        cdp.load(info.get("extras"))
         start_round = int(info.get("round") or 0) + 1 if info.get("round") is not None else 0
         obs.log(f"[server] resuming at round {start_round}")
     writer = _metrics_writer(cfg, True)
@@ -576,6 +589,7 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
         cp.set(f"r{r}/go", "1")
         dead: List[int] = []
         dropped = None  # robust rule: how often each ACCEPTED client's value was cut
+        released = True  # the round's aggregate goes into the global model
         if agg == "allreduce":
             new = cp.get_tensor(f"r{r}/avg", cfg.round_timeout_s)
             metas = [cp.get_json(f"r{r}/meta/{k}") for k in range(W)]
@@ -617,6 +631,7 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
                 if new is None:
                     obs.log(f"[server] round {r}: a client's update is non-finite; the global model is kept")
                     new = model.flat.flat.detach().clone()
+                    released = False
             else:
                 try:
                     codec.check_clients(len(ups))
@@ -632,6 +647,8 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
         dt = time.perf_counter() - t0
         rec = {"round": r, "clients_accepted": len(accepted), "clients": W, "clients_dead": dead, "round_s": dt}
         rec.update(codec.record(new.numel(), metas, dropped))
+        if cdp.active:  # A of W shares of the noise arrived: the round is accounted at z sqrt(A / W)
+            rec.update(cdp.record(len(accepted), W, spent=released))
         if "dropped_share" in rec:  # one share per client; a client not accepted has none
             by = dict(zip(accepted, rec["dropped_share"]))
             rec["dropped_share"] = [by.get(k) for k in range(W)]
@@ -647,7 +664,7 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
         obs.log(f"[server] round {r}: {len(accepted)}/{W} clients, {dt:.2f}s, auc={rec.get('valid_auc', float('nan')):.4f}")
         if cfg.snapshot_path:
             ckpt.save_snapshot(cfg.snapshot_path, model, r, round_idx=r, optim=False, config=cfg.to_dict(),
-                               server_opt=server.state())
+                               server_opt=server.state(), extras=cdp.state())
             gpath = os.path.join(os.path.dirname(os.path.abspath(cfg.snapshot_path)), f"global_model_round{r}.pt")
             ckpt.save_state_dict(gpath, model)
     R = max(cfg.global_rounds, start_round)
