@@ -20,7 +20,10 @@ snapshot): ``--upload_topk=F`` sends the ``k = max(1, ceil(F n))`` largest-magni
 round delta (``8 k`` bytes instead of ``4 n``); ``--upload_bits=8`` / ``--upload_bits=4`` sends stochastic
 8- or 4-bit codes with one fp32 scale per 256 coordinates (``n bits / 8 + 4 ceil(n / 256)`` bytes; with
 ``--upload_topk`` as well ``4 k + k bits / 8 + 4 ceil(k / 256)``).  Neither combines with
-``--secagg.enabled=1``, ``--robust_agg`` or the averaging modes.
+``--secagg.enabled=1``, ``--robust_agg`` or the averaging modes.  ``--upload_rank=R`` (1, 2, 4 or 8) sends
+every matrix of the round delta as rank-``R`` factors (``4 R (rows + cols)`` bytes instead of ``4 rows cols``;
+biases and vectors dense) and keeps its basis next to the residual in the client snapshot; it combines with
+neither of the other two, nor with ``--cdp.clip``.
 """
 from __future__ import annotations
 

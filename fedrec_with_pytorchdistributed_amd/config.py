@@ -189,6 +189,10 @@ class FedRecConfig:
     # quantisation with error feedback; ops.quantize_delta / ops.dequant_combine, parallel/quantize.py);
     # with upload_topk the selected values are quantised.  0 = fp32 values
     upload_bits: int = 0
+    # star clients upload every matrix of their round delta as rank-R factors (PowerSGD with error feedback and a
+    # warm-started basis; ops.lowrank_*, parallel/lowrank.py), biases and vectors dense; R in {1, 2, 4, 8}, alone
+    # among the compressors.  0 = off
+    upload_rank: int = 0
     pa_average_moments: bool = False  # PA: average the clients' Adam m / v with the parameters
     # unfrozen backbone (GA): reduce the gradient in ~28 MB buckets during the backward (DDP's
     # reducer, parallel/reducer.py); False = one flat all-reduce after it

@@ -84,7 +84,8 @@ OUT_SAN = PKG / "_C_san.so"
 # on gfx950.  The older files keep the flags they were tuned and measured with
 NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 KERNEL_FLAGS = {"krum": NO_PK, "geomed": NO_PK,  # geomed.hip: 16-byte a32 * x + acc, rounded per element
-                "dp_clip": NO_PK}  # dp_clip.hip: 16-byte local - base, base + s * d, p + std * z, rounded per element
+                "dp_clip": NO_PK,  # dp_clip.hip: 16-byte local - base, base + s * d, p + std * z, rounded per element
+                "lowrank_delta": NO_PK}  # lowrank_delta.hip: 16-byte (local - global) + residual right before its MFMAs
 
 
 def _clangxx() -> str:

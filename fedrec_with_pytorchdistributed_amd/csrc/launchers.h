@@ -226,6 +226,21 @@ int fr_quantize_delta(const float* local, const float* global, float* residual, 
 int fr_dequant_combine(const float* base, const unsigned char* codes, const float* scales, const float* weights,
                        float* out, int W, long n, int bits, hipStream_t s);
 
+// ---- lowrank_delta.hip -----------------------------------------------------------------------
+int fr_lowrank_project(const float* local, const float* global, const float* residual, const float* basis,
+                       float* payload, const int* mats, const int* tiles, int ntiles, int M, int R, long n, long F,
+                       int max_blocks, hipStream_t s);
+int fr_lowrank_orth(float* payload, const int* mats, int M, int R, long F, hipStream_t s);
+int fr_lowrank_backproject(const float* local, const float* global, const float* residual, float* payload, float* part,
+                           const int* mats, const int* tiles, int ntiles, const int* ftiles, int nf, int M, int R,
+                           long n, long F, int max_blocks, hipStream_t s);
+int fr_lowrank_residual(const float* local, const float* global, float* residual, float* payload, const int* mats,
+                        const int* rest, const int* tiles, int ntiles, int M, int S, int R, long n, long F, long L,
+                        int max_blocks, hipStream_t s);
+int fr_lowrank_combine(const float* base, const float* stack, const float* weights, float* out, const int* mats,
+                       const int* rest, const int* tiles, int ntiles, int M, int S, int R, int W, long n, long F, long L,
+                       int max_blocks, hipStream_t s);
+
 // ---- secagg.hip ------------------------------------------------------------------------------
 int fr_secagg_mask(const float* x, int* out, long n, float scale, float clipv, const unsigned long long* seeds,
                    const int* signs, int npeers, unsigned long long round, hipStream_t s);

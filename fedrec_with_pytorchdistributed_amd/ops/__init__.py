@@ -54,6 +54,11 @@ quantize_delta /      (beyond the reference)       quant_delta.hip: stochastic i
 dequant_combine                                    fp32 scale per 256 coordinates and the error-feedback
                                                    residual, 16 coordinates per lane in registers; W
                                                    quantised deltas dequantised onto a base
+lowrank_project /     (beyond the reference)       lowrank_delta.hip: rank-R factors of every matrix of a
+lowrank_orth /                                     round delta (PowerSGD) in one launch per stage: a Q and
+lowrank_backproject /                              a^T P^ register-direct on fp32 MFMA with a formed in
+lowrank_residual /                                 registers, Gram-Schmidt with fp64 dots, the error-feedback
+lowrank_combine                                    residual; W factor payloads decoded onto a base
 ====================  ===========================  ===========================================
 """
 from __future__ import annotations
@@ -654,3 +659,84 @@ def colsum_f32(pairs, accumulate: bool = False) -> None:
     for X, out, M, N, ld in pairs:
         ints += [int(M), int(N), int(ld), int(accumulate)]
     native.require_for(pairs[0][0]).colsum_f32([p[0] for p in pairs], [p[1] for p in pairs], ints)
+
+
+# ---------------------------------------------------------------------------------------
+# Low-rank (PowerSGD) uploads: csrc/lowrank_delta.hip.  ``plan``: an :class:`ops.reference.LowRankPlan`;
+# ``max_blocks > 0`` caps a launch's grid (no result depends on it).
+def lowrank_project(local, global_, residual, basis, payload, plan, max_blocks: int = 0):
+    """``P = a Q`` of every matrix of the plan, written into ``payload`` at the place of ``P^``; ``a = (local -
+    global_) + residual`` is formed in registers, ``Q`` is read from ``basis [F]`` (the payload's factor layout).
+    One launch over all matrices on the fp32 matrix cores.  A tolerance contract: per element the error against
+    the exact product of the same fp32 ``a`` and ``Q`` is within the dot-product bound ``(cols + 2) 2^-24 (|a|
+    |Q|)``; bitwise independent of the grid.  The host form: :func:`ops.reference.lowrank_project`."""
+    if _dev(residual):
+        native.require_for(residual)
+        t = plan.on(residual.device)
+        torch.ops.fedrec_lowrank.project(local, global_, residual, basis, payload, t["mats"], t["tiles_p"], plan.rank,
+                                         int(max_blocks))
+        return payload
+    return ref.lowrank_project(local, global_, residual, basis, payload, plan)
+
+
+def lowrank_orth(payload, plan):
+    """``P^ = orth(P)`` in place: modified Gram-Schmidt, every column projected twice, dots and norms in fp64 in a
+    fixed order; a column that vanishes under projection (squared norm ``0`` or ``<= 2^-40`` of the one before)
+    becomes zeros, so a rank-deficient delta gives zero columns and no NaN.  One workgroup per matrix.  A
+    tolerance contract.  The host form and the exact rule: :func:`ops.reference.lowrank_orth`."""
+    if _dev(payload):
+        native.require_for(payload)
+        torch.ops.fedrec_lowrank.orth(payload, plan.on(payload.device)["mats"], plan.rank, plan.F)
+        return payload
+    return ref.lowrank_orth(payload, plan)
+
+
+def lowrank_backproject(local, global_, residual, payload, plan, max_blocks: int = 0):
+    """``Q' = a^T P^`` of every matrix, written into ``payload`` at the place of ``Q'`` (``P^`` is read from it).
+    Row chunks of 256 are a function of the shape alone and are added in ascending order: bitwise independent of
+    the grid.  A tolerance contract: the dot-product bound with ``rows`` as the length.  The host form:
+    :func:`ops.reference.lowrank_backproject`."""
+    if _dev(residual):
+        native.require_for(residual)
+        t = plan.on(residual.device)
+        torch.ops.fedrec_lowrank.backproject(local, global_, residual, payload, t["mats"], t["tiles_b"], t["tiles_f"],
+                                             plan.rank, plan.F, int(max_blocks))
+        return payload
+    return ref.lowrank_backproject(local, global_, residual, payload, plan)
+
+
+def lowrank_residual(local, global_, residual, payload, plan, max_blocks: int = 0):
+    """The end of a client's round, in place: ``residual = a - d`` on the matrices with ``d_ij = sum over t < R,
+    ascending, of P^_it Q'_jt`` (every product and sum rounded on its own), and on the rest ``payload = a``,
+    ``residual = +0.0``.  A bitwise contract between the kernel and :func:`ops.reference.lowrank_residual`."""
+    if _dev(residual):
+        native.require_for(residual)
+        t = plan.on(residual.device)
+        torch.ops.fedrec_lowrank.residual(local, global_, residual, payload, t["mats"], t["rest"], t["tiles_e"], plan.rank,
+                                          plan.F, int(max_blocks))
+        return payload
+    return ref.lowrank_residual(local, global_, residual, payload, plan)
+
+
+def lowrank_compress(local, global_, residual, basis, plan):
+    """One client round -> the payload fp32 ``[plan.L]``; ``residual`` is updated in place, ``basis`` is read.
+    project, orth, backproject and residual: five launches in all, no host synchronisation between them."""
+    payload = torch.zeros(plan.L, dtype=torch.float32, device=residual.device)
+    lowrank_project(local, global_, residual, basis, payload, plan)
+    lowrank_orth(payload, plan)
+    lowrank_backproject(local, global_, residual, payload, plan)
+    return lowrank_residual(local, global_, residual, payload, plan)
+
+
+def lowrank_combine(base, stack, weights, plan, max_blocks: int = 0):
+    """``W`` low-rank uploads ``stack [W, plan.L]`` applied to ``base [n]`` fp32 -> ``out [n]``: ``out = base +
+    (sum over c, in client order, of weights[c] * d_c) / sum(weights)``, ``d_c`` decoded exactly as
+    :func:`lowrank_residual` decodes it and rounded as :func:`dequant_combine` rounds.  The kernel stays inside the
+    plan whatever the payloads hold.  A bitwise contract: the coordinator (host) and clients that combine among
+    themselves (device) hold the same bits.  The host form: :func:`ops.reference.lowrank_combine`."""
+    if _dev(base):
+        native.require_for(base)
+        t = plan.on(base.device)
+        return torch.ops.fedrec_lowrank.combine(base, stack, weights, t["mats"], t["rest"], t["tiles_e"], plan.rank, plan.F,
+                                                int(max_blocks))
+    return ref.lowrank_combine(base, stack, weights, plan)

@@ -1161,3 +1161,200 @@ def quant_upload_check(codes: torch.Tensor, scales: torch.Tensor, n: int, bits: 
     if bad.numel():
         j = int(bad[0])
         raise ValueError(f"quantized upload: scales[{j}] = {float(scales[j])} is not a finite value >= +0.0")
+
+
+# ---------------------------------------------------------------------------------------
+# Low-rank (PowerSGD) uploads with error feedback (oracle of csrc/lowrank_delta.hip)
+# ---------------------------------------------------------------------------------------
+LOWRANK_RANKS = (1, 2, 4, 8)
+
+
+class LowRankPlan:
+    """Which coordinates of a padded flat buffer travel as rank-``R`` factors and which dense: a pure function of
+    the layout and ``R``, so a client and the coordinator derive the same one.
+
+    ``layout``: ``(offset, shape)`` of every parameter, offsets ascending, inside ``[0, n)``.  A parameter is a
+    matrix of the plan when it is 2-D, ``min(rows, cols) >= 16`` and ``R (rows + cols) <= rows cols / 2``; every
+    other coordinate of ``[0, n)`` (biases, vectors, the alignment padding) is "rest".  The payload is fp32 ``[L]``:
+    per matrix ``P^ [rows, R]`` at ``fac`` and ``Q' [cols, R]`` at ``fac + rows R`` (the factors fill ``[0, F)``),
+    then the rest segments' values.  ``mats`` int32 ``[M, 4]``: flat offset, rows, cols, ``fac``; ``rest`` int32
+    ``[S, 3]``: flat start, length, payload offset.  The tile tables are the kernels' (csrc/lowrank_delta.hip):
+    ``tiles_p [*, 2]`` 16 rows of a matrix; ``tiles_b [*, 3]`` 64 columns x a chunk of 256 rows and ``tiles_f [*,
+    4]`` a column group's chunks; ``tiles_e [*, 3]`` 32 x 256 of a matrix or 1024 elements of a rest segment."""
+
+    def __init__(self, layout, n: int, rank: int):
+        if rank not in LOWRANK_RANKS:
+            raise ValueError(f"upload_rank={rank}: expected one of {LOWRANK_RANKS}")
+        R, n = int(rank), int(n)
+        if not 1 <= n < 2 ** 31:
+            raise ValueError(f"low-rank plan: 1 <= n < 2^31 (got n {n})")
+        mats, rest, fac, end = [], [], 0, 0
+        for off, shape in layout:
+            off, numel = int(off), int(math.prod(shape))
+            if off < end or off + numel > n:
+                raise ValueError(f"low-rank plan: parameter at {off} of {numel} elements overlaps its neighbour or ends past {n}")
+            if len(shape) == 2 and min(shape) >= 16 and 2 * R * (shape[0] + shape[1]) <= shape[0] * shape[1]:
+                if off > end:
+                    rest.append([end, off - end])
+                mats.append([off, int(shape[0]), int(shape[1]), fac])
+                fac += R * (shape[0] + shape[1])
+                end = off + numel
+        if n > end:
+            rest.append([end, n - end])
+        if not mats:
+            raise ValueError(f"low-rank plan: no parameter of the layout is a matrix to factor at rank {R}")
+        self.rank, self.n, self.F = R, n, fac
+        pay = fac
+        for seg in rest:
+            seg.append(pay)
+            pay += seg[1]
+        self.L = pay
+        tp, tb, tf, te = [], [], [], []
+        for m, (off, rows, cols, _) in enumerate(mats):
+            tp += [[m, r0] for r0 in range(0, rows, 16)]
+            nch = -(-rows // 256)
+            for c0 in range(0, cols, 64):
+                tf.append([m, c0, len(tb), nch])
+                tb += [[m, c0, ch] for ch in range(nch)]
+            te += [[m, r0, c0] for r0 in range(0, rows, 32) for c0 in range(0, cols, 256)]
+        for s, (_, ln, _) in enumerate(rest):
+            te += [[-1 - s, e0, 0] for e0 in range(0, ln, 1024)]
+        i32 = lambda rows, w: torch.tensor(rows, dtype=torch.int32).reshape(-1, w)  # noqa: E731
+        self.tables = {"mats": i32(mats, 4), "rest": i32(rest, 3), "tiles_p": i32(tp, 2), "tiles_b": i32(tb, 3),
+                       "tiles_f": i32(tf, 4), "tiles_e": i32(te, 3)}
+        self.mats, self.rest = [tuple(r) for r in mats], [tuple(r) for r in rest]
+        self._on = {}
+
+    def on(self, device) -> dict:
+        """The tables on ``device`` (copied once)."""
+        device = torch.device(device)
+        if device not in self._on:
+            self._on[device] = {k: t.to(device) for k, t in self.tables.items()}
+        return self._on[device]
+
+    def factors(self, payload: torch.Tensor, m: int):
+        """Views ``(P^ [rows, R], Q' [cols, R])`` of matrix ``m`` in a payload (or a basis)."""
+        _, rows, cols, fac = self.mats[m]
+        R = self.rank
+        return payload[fac:fac + rows * R].view(rows, R), payload[fac + rows * R:fac + (rows + cols) * R].view(cols, R)
+
+    def initial_basis(self, seed: int) -> torch.Tensor:
+        """The round-1 basis ``[F]`` on the host: ``Q`` of matrix ``m`` standard normal from a generator seeded by
+        ``(seed, m)``, at the place of ``Q'``; zeros at the place of ``P^``."""
+        basis = torch.zeros(self.F, dtype=torch.float32)
+        for m in range(len(self.mats)):
+            g = torch.Generator().manual_seed((int(seed) * 1_000_003 + m) & 0x7FFFFFFFFFFF)
+            q = self.factors(basis, m)[1]
+            q.copy_(torch.randn(q.shape, generator=g, dtype=torch.float32))
+        return basis
+
+
+def _lowrank_check(plan: LowRankPlan, op: str, payload: torch.Tensor, *flats: torch.Tensor) -> None:
+    for t in flats:
+        _check_vec(t, op, "a flat tensor")
+        if t.numel() != plan.n:
+            raise RuntimeError(f"{op}: local, global, residual and base must have the plan's {plan.n} elements (got {t.numel()})")
+    if payload.dim() != 1 or payload.numel() < plan.F:
+        raise RuntimeError(f"{op}: the payload must be 1-D with at least the plan's {plan.F} factor elements")
+
+
+def _lowrank_a(local, global_, residual, off: int, rows: int, cols: int) -> torch.Tensor:
+    s = slice(off, off + rows * cols)
+    return ((local[s] - global_[s]) + residual[s]).view(rows, cols)
+
+
+def lowrank_project(local, global_, residual, basis, payload, plan: LowRankPlan) -> torch.Tensor:
+    """``P = a Q`` of every matrix of the plan into ``payload`` (at the place of ``P^``), ``a = (local - global_) +
+    residual`` in fp32 and ``Q`` from ``basis`` (the payload's factor layout).  A tolerance contract: the order of
+    a dot product's sum is the implementation's."""
+    _lowrank_check(plan, "lowrank_project", payload, local, global_, residual)
+    for m, (off, rows, cols, _) in enumerate(plan.mats):
+        plan.factors(payload, m)[0].copy_(_lowrank_a(local, global_, residual, off, rows, cols) @ plan.factors(basis, m)[1])
+    return payload
+
+
+def lowrank_orth(payload, plan: LowRankPlan) -> torch.Tensor:
+    """``P^ = orth(P)`` in place, per matrix: modified Gram-Schmidt over the ``R`` columns in order.  Column ``c``
+    is projected against columns ``0 .. c - 1`` in order, twice (re-orthogonalisation): ``v -= <p_b, v> p_b`` with
+    the dot product and the update in fp64, the column rounded to the payload's type after every update.  With
+    ``n0`` and ``n1`` the column's squared norms (fp64) before and after, ``n1 == 0`` or ``n1 <= 2^-40 n0`` makes it
+    a zero column, else it is divided by ``sqrt(n1)`` in fp64 and rounded.  A payload of fp64 keeps every value
+    in fp64: the same algorithm as its own high-precision oracle."""
+    if payload.dim() != 1 or payload.numel() < plan.F:
+        raise RuntimeError(f"lowrank_orth: the payload must be 1-D with at least the plan's {plan.F} factor elements")
+    for m in range(len(plan.mats)):
+        P = plan.factors(payload, m)[0]
+        for c in range(plan.rank):
+            v = P[:, c].double()
+            n0 = (v * v).sum()
+            for _ in range(2):
+                for b in range(c):
+                    pb = P[:, b].double()
+                    v = (v - (pb * v).sum() * pb).to(P.dtype).double()
+            n1 = (v * v).sum()
+            zero = bool(n1 == 0) or bool(n1 <= 2.0 ** -40 * n0)
+            P[:, c] = torch.zeros_like(P[:, c]) if zero else (v / torch.sqrt(n1)).to(P.dtype)
+    return payload
+
+
+def lowrank_backproject(local, global_, residual, payload, plan: LowRankPlan) -> torch.Tensor:
+    """``Q' = a^T P^`` of every matrix into ``payload`` (at the place of ``Q'``).  A tolerance contract."""
+    _lowrank_check(plan, "lowrank_backproject", payload, local, global_, residual)
+    for m, (off, rows, cols, _) in enumerate(plan.mats):
+        P, Q = plan.factors(payload, m)
+        Q.copy_(_lowrank_a(local, global_, residual, off, rows, cols).t() @ P)
+    return payload
+
+
+def lowrank_decode(payload, plan: LowRankPlan, m: int) -> torch.Tensor:
+    """``d [rows, cols]`` of matrix ``m``: ``d_ij = P^_i0 Q'_j0``, then ``+ P^_it Q'_jt`` for ``t = 1 .. R - 1`` in
+    order, every product and every sum rounded on its own (no FMA)."""
+    P, Q = plan.factors(payload, m)
+    d = P[:, 0:1] * Q[:, 0][None, :]
+    for t in range(1, plan.rank):
+        d = d + P[:, t:t + 1] * Q[:, t][None, :]
+    return d
+
+
+def lowrank_residual(local, global_, residual, payload, plan: LowRankPlan) -> torch.Tensor:
+    """The end of a client's round, ``residual`` and ``payload`` in place: on a matrix ``residual = a -
+    decode(payload)`` (:func:`lowrank_decode`; one fp32 subtraction); on the rest ``payload = a`` and ``residual =
+    +0.0``.  A bitwise contract."""
+    _lowrank_check(plan, "lowrank_residual", payload, local, global_, residual)
+    if payload.numel() != plan.L:
+        raise RuntimeError(f"lowrank_residual: the payload must have the plan's {plan.L} elements (got {payload.numel()})")
+    for m, (off, rows, cols, _) in enumerate(plan.mats):
+        a = _lowrank_a(local, global_, residual, off, rows, cols)
+        residual[off:off + rows * cols] = (a - lowrank_decode(payload, plan, m)).reshape(-1)
+    for start, ln, pay in plan.rest:
+        s = slice(start, start + ln)
+        payload[pay:pay + ln] = (local[s] - global_[s]) + residual[s]
+        residual[s] = 0.0
+    return payload
+
+
+def lowrank_combine(base, stack, weights, plan: LowRankPlan) -> torch.Tensor:
+    """``W`` low-rank uploads ``stack [W, L]`` applied to ``base [n]`` -> ``out [n]`` fp32: ``acc`` starts at
+    ``+0.0``; for ``c = 0 .. W - 1`` in that order ``acc += weights[c] * d_c`` (product and sum rounded on their
+    own) with ``d_c`` the decoded matrix (:func:`lowrank_decode`) or the dense rest value; ``wsum`` is the
+    sequential fp32 sum of the weights from ``+0.0``; ``out = base + acc / wsum``.  A bitwise contract."""
+    _lowrank_check(plan, "lowrank_combine", stack[0] if stack.dim() == 2 and stack.shape[0] else stack, base)
+    if stack.dim() != 2 or stack.shape[1] != plan.L or weights.numel() != stack.shape[0]:
+        raise RuntimeError(f"lowrank_combine: stack [W, {plan.L}] and weights [W] (got {tuple(stack.shape)}, {weights.numel()})")
+    out = base.clone()
+    ws = torch.zeros((), dtype=torch.float32)
+    for c in range(stack.shape[0]):
+        ws = ws + weights[c]
+    for m, (off, rows, cols, _) in enumerate(plan.mats):
+        acc = torch.zeros(rows, cols, dtype=torch.float32)
+        for c in range(stack.shape[0]):
+            acc = acc + weights[c] * lowrank_decode(stack[c], plan, m)
+        s = slice(off, off + rows * cols)
+        out[s] = base[s] + (acc / ws).reshape(-1)
+    for start, ln, pay in plan.rest:
+        acc = torch.zeros(ln, dtype=torch.float32)
+        for c in range(stack.shape[0]):
+            acc = acc + weights[c] * stack[c, pay:pay + ln]
+        s = slice(start, start + ln)
+        out[s] = base[s] + acc / ws
+    return out

@@ -1,6 +1,8 @@
 """The form of a star client's upload, chosen once per run (:meth:`StarUpload.from_cfg`): the dense fp32 model
-(under the robust rule of parallel/robust.py, when one is set), the top-k list of parallel/sparsify.py or the
-quantised codes of parallel/quantize.py -- one interface, so that the star drivers hold one path for all three.
+(under the robust rule of parallel/robust.py, when one is set), the top-k list of parallel/sparsify.py, the
+quantised codes of parallel/quantize.py or the low-rank factors of parallel/lowrank.py -- one interface, so that the
+star drivers hold one path for all four.  ``bind(flat_params)``, once after the model is built, gives a codec the
+layout of the flat buffer (only the low-rank one needs it).
 
 ``compress(local, theta_g, residual, client, round)`` makes the payload (the flat model, ``(idx, val)``, an ``Upload``),
 ``finite`` tells whether a coordinator may take it, ``pack`` / ``unpack(blob, n)`` are its wire tensor (``unpack``
@@ -25,16 +27,25 @@ class StarUpload:
     uses_residual = True  # the driver keeps an fp32 error-feedback residual (checkpointed as UPLOAD_RESIDUAL)
     options: dict = {}  # the option keys of this form in a round record
     rule = RobustRule()  # (inactive: the dense codec holds the run's)
+    basis = None  # the low-rank codec's per-matrix basis (checkpointed as UPLOAD_BASIS); None on the others
 
     @staticmethod
     def from_cfg(cfg, driver: str) -> "StarUpload":
         """The codec of ``cfg``; every option is rejected where it cannot hold (``driver``: the federation
         driver that asks).  Outside the star only the dense codec's ``rule`` means anything."""
-        from .quantize import Quantizer  # (a StarUpload itself: quantize.py imports this module)
+        from .lowrank import LowRank  # (StarUploads themselves: both modules import this one)
+        from .quantize import Quantizer
         rule = RobustRule.from_cfg(cfg, driver)
         sparse = Sparsifier.from_cfg(cfg, driver)
         quant = Quantizer.from_cfg(cfg, driver)
+        low = LowRank.from_cfg(cfg, driver)
+        if low.active:
+            return low
         return quant if quant.active else TopkUpload(sparse) if sparse.active else DenseUpload(rule)
+
+    def bind(self, flat_params) -> "StarUpload":
+        """Called once with the model's ``FlatParams``: a codec that needs the layout plans here."""
+        return self
 
     def check_clients(self, W: int) -> None:
         """``ValueError`` where ``W`` payloads are too few to combine."""

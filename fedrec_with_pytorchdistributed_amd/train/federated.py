@@ -23,7 +23,8 @@ all-gathers, and the records gain ``dropped_share`` (how often each client's val
 
 What a star client uploads is the run's codec (parallel/upload.py, ``StarUpload.from_cfg``): the dense model, with
 ``cfg.upload_topk`` the largest-magnitude fraction of its round delta, with ``cfg.upload_bits`` stochastic 8- or 4-bit
-codes of it; what was not sent stays in a residual for the next round (error feedback), and the records gain
+codes of it, with ``cfg.upload_rank`` rank-R factors of every matrix of it (parallel/lowrank.py); what was not sent
+stays in a residual for the next round (error feedback), and the records gain
 ``upload_bytes`` / ``dense_bytes``.  A round's tail is secure aggregation or the codec, among the clients
 (``combine_among``) or through the coordinator (``pack`` -> store -> ``unpack`` / ``combine``).
 
@@ -384,7 +385,7 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
     model = build_model(cfg, ctx.device)  # created ONCE: Adam moments persist across rounds
     eng = LocalEngine(cfg, model, shard, ctx.device, rank=ctx.rank, grad_allreduce=None)
     fault = FaultInjector("client", k)
-    codec = StarUpload.from_cfg(cfg, "fedavg_star")
+    codec = StarUpload.from_cfg(cfg, "fedavg_star").bind(model.flat)
     cdp = ClientDP.from_cfg(cfg, "fedavg_star", ctx.num_clients)  # client-level DP: clip + noise before the upload
     # what top-k sparsification / quantisation has not sent yet (error feedback); zero at the start
     residual = torch.zeros_like(model.flat.flat, dtype=torch.float32) if codec.uses_residual else None
@@ -410,12 +411,15 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
         obs.log(f"[client {k}] save_every={cfg.save_every} does not apply to client snapshots: they are written "
                 "every round (a resume from an older round would redraw LDP noise / dropout already uploaded)")
     if csnap and os.path.exists(csnap):
-        info = ckpt.load_client_state(csnap, model, residual)
+        info = ckpt.load_client_state(csnap, model, residual, codec.basis)
         eng.load_state(info["engine"])
         obs.log(f"[client {k}] resumed {csnap} (round {info['round']}, Adam step {model.flat.step})")
         if residual is not None and not info.get("residual_restored"):
             obs.log(f"[client {k}] {csnap} holds no upload residual of {residual.numel()} elements: resuming with a "
                     "zero residual")
+        if codec.basis is not None and not info.get("basis_restored"):
+            obs.log(f"[client {k}] {csnap} holds no upload basis of {codec.basis.numel()} elements: resuming with the "
+                    "round-1 basis")
     beat = Heartbeat(cp, f"client{k}", cfg.heartbeat_s)
     # model sync (server.py:76-77 / client.py:261-264): client 0 alone reads the coordinator's
     # global model from the store and broadcasts it over the client data group (RCCL over
@@ -522,7 +526,7 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
             # full state with the frozen backbone).  Every round, not every save_every: a resume
             # from an older round would redraw the LDP noise / dropout of the rounds in between
             # at the same offsets, and noise that was already uploaded must never be reused
-            ckpt.save_client_state(csnap, model, r, eng.state(), residual)
+            ckpt.save_client_state(csnap, model, r, eng.state(), residual, codec.basis)
         last = meta
         r += 1
     _dump_flat(model, ctx)
@@ -566,7 +570,7 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
     W = ctx.num_clients
     model = build_model(cfg, torch.device("cpu"))
     server = ServerStep.from_cfg(cfg)  # off by default: the plain mean
-    codec = StarUpload.from_cfg(cfg, "fedavg_star")  # (dense under secure aggregation: its uploads pass as they are)
+    codec = StarUpload.from_cfg(cfg, "fedavg_star").bind(model.flat)  # (dense under secure aggregation: its uploads pass as they are)
     cdp = ClientDP.from_cfg(cfg, "fedavg_star", W)  # here: the accountant of what the clients clipped and noised
     start_round = 0
     if cfg.snapshot_path and os.path.exists(cfg.snapshot_path):
