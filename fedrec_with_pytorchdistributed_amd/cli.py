@@ -23,7 +23,10 @@ round delta (``8 k`` bytes instead of ``4 n``); ``--upload_bits=8`` / ``--upload
 ``--secagg.enabled=1``, ``--robust_agg`` or the averaging modes.  ``--upload_rank=R`` (1, 2, 4 or 8) sends
 every matrix of the round delta as rank-``R`` factors (``4 R (rows + cols)`` bytes instead of ``4 rows cols``;
 biases and vectors dense) and keeps its basis next to the residual in the client snapshot; it combines with
-neither of the other two, nor with ``--cdp.clip``.
+neither of the other two, nor with ``--cdp.clip``.  ``--upload_sketch=F`` sends the count sketch of the round delta
+(``--upload_sketch_rows`` x ``--upload_sketch_cols`` buckets, ``4 R C`` bytes) and keeps no client state: the tables
+are added, ``k = max(1, ceil(F n))`` coordinates are recovered per round and the error table stays with whoever
+combines; it combines with none of the other three, and alone among them with ``--cdp.clip``.
 """
 from __future__ import annotations
 

@@ -193,6 +193,14 @@ class FedRecConfig:
     # warm-started basis; ops.lowrank_*, parallel/lowrank.py), biases and vectors dense; R in {1, 2, 4, 8}, alone
     # among the compressors.  0 = off
     upload_rank: int = 0
+    # star clients upload a count sketch of their round delta (FetchSGD; ops.sketch_*, parallel/sketch.py): a table of
+    # upload_sketch_rows (1, 3 or 5) x upload_sketch_cols buckets (0: the smallest power of two >= max(1024, 4 k);
+    # else a power of two >= 1024; rows x cols < n).  The tables are added, and k = ceil(upload_sketch * n)
+    # coordinates are recovered per round; the clients keep no residual (the error table stays with whoever
+    # combines), so it alone among the compressors combines with cdp.clip.  0 = off
+    upload_sketch: float = 0.0
+    upload_sketch_rows: int = 5
+    upload_sketch_cols: int = 0
     pa_average_moments: bool = False  # PA: average the clients' Adam m / v with the parameters
     # unfrozen backbone (GA): reduce the gradient in ~28 MB buckets during the backward (DDP's
     # reducer, parallel/reducer.py); False = one flat all-reduce after it

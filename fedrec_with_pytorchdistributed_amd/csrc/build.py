@@ -85,7 +85,8 @@ OUT_SAN = PKG / "_C_san.so"
 NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 KERNEL_FLAGS = {"krum": NO_PK, "geomed": NO_PK,  # geomed.hip: 16-byte a32 * x + acc, rounded per element
                 "dp_clip": NO_PK,  # dp_clip.hip: 16-byte local - base, base + s * d, p + std * z, rounded per element
-                "lowrank_delta": NO_PK}  # lowrank_delta.hip: 16-byte (local - global) + residual right before its MFMAs
+                "lowrank_delta": NO_PK,  # lowrank_delta.hip: 16-byte (local - global) + residual right before its MFMAs
+                "sketch_delta": NO_PK}  # sketch_delta.hip: 16-byte local - global and acc + w * s, rounded per element
 
 
 def _clangxx() -> str:

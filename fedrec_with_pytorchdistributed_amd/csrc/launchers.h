@@ -241,6 +241,13 @@ int fr_lowrank_combine(const float* base, const float* stack, const float* weigh
                        const int* rest, const int* tiles, int ntiles, int M, int S, int R, int W, long n, long F, long L,
                        int max_blocks, hipStream_t s);
 
+// ---- sketch_delta.hip ------------------------------------------------------------------------
+int fr_sketch_delta(const float* local, const float* global, const int* plan, float* S, long n, int nb, int R, long C,
+                    hipStream_t s);
+int fr_sketch_estimate(const float* S, const int* plan, float* est, long n, int nb, int R, long C, hipStream_t s);
+int fr_sketch_accumulate(float* E, const float* stack, const float* weights, int W, long L, hipStream_t s);
+int fr_sketch_clear(float* E, const int* idx, const int* plan, long k, int nb, int R, long C, hipStream_t s);
+
 // ---- secagg.hip ------------------------------------------------------------------------------
 int fr_secagg_mask(const float* x, int* out, long n, float scale, float clipv, const unsigned long long* seeds,
                    const int* signs, int npeers, unsigned long long round, hipStream_t s);

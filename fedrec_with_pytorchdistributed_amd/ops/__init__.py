@@ -59,6 +59,11 @@ lowrank_orth /                                     round delta (PowerSGD) in one
 lowrank_backproject /                              a^T P^ register-direct on fp32 MFMA with a formed in
 lowrank_residual /                                 registers, Gram-Schmidt with fp64 dots, the error-feedback
 lowrank_combine                                    residual; W factor payloads decoded onto a base
+sketch_delta /        (beyond the reference)       sketch_delta.hip: the count sketch of a round delta (FetchSGD)
+sketch_estimate /                                  under a block-permutation hash: a tile of buckets gathers its
+sketch_accumulate_ /                               one coordinate per block from an LDS ring in block order (no
+sketch_clear_                                      atomics); the median-of-rows estimate from table tiles in LDS;
+                                                   W tables added onto the error table; recovered buckets zeroed
 ====================  ===========================  ===========================================
 """
 from __future__ import annotations
@@ -740,3 +745,49 @@ def lowrank_combine(base, stack, weights, plan, max_blocks: int = 0):
         return torch.ops.fedrec_lowrank.combine(base, stack, weights, t["mats"], t["rest"], t["tiles_e"], plan.rank, plan.F,
                                                 int(max_blocks))
     return ref.lowrank_combine(base, stack, weights, plan)
+
+
+# ---------------------------------------------------------------------------------------
+# Count-sketch (FetchSGD) uploads: csrc/sketch_delta.hip.  ``plan``: the int32 ``[nb, 8, 4]`` hash words of
+# :func:`ops.reference.sketch_plan`, on the device of the other tensors.
+def sketch_delta(local, global_, plan, rows: int, cols: int):
+    """The count sketch ``S [rows, cols]`` fp32 of the round delta ``local - global_`` (``[n]`` fp32 contiguous; a
+    view such as ``x[1:]`` is fine): every bucket adds ``+-a_i`` of its one coordinate per block of ``cols``
+    coordinates, the blocks in ascending order, one fp32 addition each.  Linear in the delta up to rounding: the
+    sketch of a weighted sum is the weighted sum of the sketches.  No atomics, bitwise a function of the inputs and
+    ``(n, rows, cols, seed)`` alone (csrc/sketch_delta.hip).  The exact contract: :func:`ops.reference.sketch_delta`."""
+    if _dev(local):
+        native.require_for(local)
+        return torch.ops.fedrec_sketch.delta(local, global_, plan, int(rows), int(cols))
+    return ref.sketch_delta(local, global_, plan, int(rows), int(cols))
+
+
+def sketch_estimate(table, plan, n: int):
+    """``est [n]`` fp32 from a sketch ``table [rows, cols]``: per coordinate the median over the rows of its signed
+    bucket, under the total order of :func:`ops.reference.order_keys`.  Exact: the device and
+    :func:`ops.reference.sketch_estimate` hold the same bits."""
+    if _dev(table):
+        native.require_for(table)
+        return torch.ops.fedrec_sketch.estimate(table, plan, int(n))
+    return ref.sketch_estimate(table, plan, int(n))
+
+
+def sketch_accumulate_(table, stack, weights):
+    """In place ``table += (sum over c, in client order, of weights[c] * stack[c]) / sum(weights)``; ``stack [W,
+    table.numel()]``, ``W <= 32``; rounded as :func:`dequant_combine` rounds.  The exact contract:
+    :func:`ops.reference.sketch_accumulate_`."""
+    if _dev(table):
+        native.require_for(table)
+        torch.ops.fedrec_sketch.accumulate_(table, stack, weights)
+        return table
+    return ref.sketch_accumulate_(table, stack, weights)
+
+
+def sketch_clear_(table, idx, plan):
+    """In place ``table[r, h_r(i)] = +0.0`` for every ``i`` of ``idx [k]`` int32 and every row (an index outside the
+    plan's blocks is skipped).  The exact contract: :func:`ops.reference.sketch_clear_`."""
+    if _dev(table):
+        native.require_for(table)
+        torch.ops.fedrec_sketch.clear_(table, idx, plan)
+        return table
+    return ref.sketch_clear_(table, idx, plan)

@@ -1358,3 +1358,173 @@ def lowrank_combine(base, stack, weights, plan: LowRankPlan) -> torch.Tensor:
         s = slice(start, start + ln)
         out[s] = base[s] + acc / ws
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# Count-sketch (FetchSGD) uploads (oracle of csrc/sketch_delta.hip)
+# ---------------------------------------------------------------------------------------
+SKETCH_T = 1024  # the tile: coordinates of one (block, tile) pair share their hash words
+SKETCH_ROWS = (1, 3, 5)
+SKETCH_STREAM = 0x736B657463680001  # the Philox offset of the hash words ("sketch", version 1)
+
+
+def _wrap_i32(x: torch.Tensor) -> torch.Tensor:
+    """uint32 values held in int64 -> the int32 with the same bits."""
+    return (((x & _U32) + 2 ** 31) % 2 ** 32 - 2 ** 31).to(torch.int32)
+
+
+def fmix32(h: torch.Tensor) -> torch.Tensor:
+    """The murmur3 finaliser on uint32 values held in int64."""
+    h = h & _U32
+    h = ((h ^ (h >> 16)) * 0x85EBCA6B) & _U32
+    h = ((h ^ (h >> 13)) * 0xC2B2AE35) & _U32
+    return h ^ (h >> 16)
+
+
+def sketch_cols_for(k: int) -> int:
+    """The smallest power of two ``>= max(1024, 4 k)``."""
+    return 1 << max(10, (4 * int(k) - 1).bit_length())
+
+
+def sketch_plan(n: int, cols: int, seed: int) -> torch.Tensor:
+    """The hash of a count sketch of ``n`` coordinates with ``cols`` buckets per row, as its words: int32 ``[nb, 8,
+    4]``, ``nb = ceil(n / cols)``.  A pure function of ``(n, cols, seed)``.
+
+    Coordinate ``i`` is ``(q, p_hi, p_lo) = (i / C, (i % C) / T, i % T)`` with ``T = 1024``, and row ``r`` sends it
+    to bucket ``j_hi T + j_lo``: ``j_hi = (p_hi + rot_q) & (C / T - 1)`` (one tile rotation per block, shared by the
+    rows), ``j_lo = (p_lo m + o) & (T - 1)`` with ``m`` odd, and gives it the sign ``-1`` iff bit 31 of
+    ``fmix32(uint32(i) ^ sx)`` is set.  Slot ``r < 5`` of block ``q`` holds ``(m, o, sx, minv)`` of row ``r`` --
+    ``philox4x32(seed, SKETCH_STREAM, 8 q + r)``'s words 0, 1, 2 (``m = word 0 | 1``, ``o = word 1 & (T - 1)``) and
+    ``minv``, the inverse of ``m`` modulo 2^32: ``p_lo = ((j_lo - o) minv) & (T - 1)``; slot 7 holds ``rot_q`` (word 0
+    of counter ``8 q + 7``) and zeros.  Inside a block every row is a bijection onto the row's buckets, so a bucket
+    takes exactly one coordinate of every block and a kernel can gather them in block order."""
+    n, C = int(n), int(cols)
+    if C < SKETCH_T or C & (C - 1):
+        raise ValueError(f"sketch plan: cols must be a power of two >= {SKETCH_T} (got {C})")
+    if not 1 <= n < 2 ** 31:
+        raise ValueError(f"sketch plan: 1 <= n < 2^31 (got n {n})")
+    nb = -(-n // C)
+    w = philox4x32(int(seed), SKETCH_STREAM, torch.arange(nb * 8, dtype=torch.int64)).view(nb, 8, 4)
+    m = w[:, :, 0] | 1
+    minv = m.clone()  # Newton: five steps double 3 correct bits to 96 >= 32
+    for _ in range(5):
+        minv = (minv * ((2 - m * minv) & _U32)) & _U32
+    plan = torch.stack([m, w[:, :, 1] & (SKETCH_T - 1), w[:, :, 2], minv], -1)
+    plan[:, 5:] = 0
+    plan[:, 7, 0] = w[:, 7, 0]
+    return _wrap_i32(plan)
+
+
+def sketch_hash(plan: torch.Tensor, i: torch.Tensor, rows: int, cols: int):
+    """Coordinates ``i`` (int64, inside the plan's blocks) -> ``(bucket [rows, len] int64, negative [rows, len]
+    bool)`` by the forward hash of :func:`sketch_plan`."""
+    T, C = SKETCH_T, int(cols)
+    w = plan.to(torch.int64) & _U32
+    q, p_hi, p_lo = i // C, (i % C) // T, i % T
+    j_hi = (p_hi + w[q, 7, 0]) & (C // T - 1)
+    j, neg = [], []
+    for r in range(int(rows)):
+        j.append(j_hi * T + ((p_lo * w[q, r, 0] + w[q, r, 1]) & (T - 1)))
+        neg.append(fmix32(i ^ w[q, r, 2]) >> 31 != 0)
+    return torch.stack(j), torch.stack(neg)
+
+
+def _flip(v: torch.Tensor, neg: torch.Tensor) -> torch.Tensor:
+    """``v`` with its sign bit flipped where ``neg`` (exact for every value, a NaN included)."""
+    b = v.contiguous().view(torch.int32)
+    return torch.where(neg, b ^ -2 ** 31, b).view(torch.float32)
+
+
+def _sketch_check(op: str, plan: torch.Tensor, n: int, rows: int, cols: int) -> None:
+    if rows not in SKETCH_ROWS:
+        raise RuntimeError(f"{op}: rows must be 1, 3 or 5 (got {rows})")
+    if cols < SKETCH_T or cols & (cols - 1):
+        raise RuntimeError(f"{op}: cols must be a power of two >= {SKETCH_T} (got {cols})")
+    if not 1 <= n < 2 ** 31:
+        raise RuntimeError(f"{op}: 1 <= n < 2^31 (got n {n})")
+    if plan.dtype != torch.int32 or tuple(plan.shape) != (-(-n // cols), 8, 4) or not plan.is_contiguous():
+        raise RuntimeError(f"{op}: plan must be a contiguous int32 [{-(-n // cols)}, 8, 4] tensor (got {plan.dtype} "
+                           f"{tuple(plan.shape)})")
+
+
+def sketch_delta(local: torch.Tensor, global_: torch.Tensor, plan: torch.Tensor, rows: int, cols: int) -> torch.Tensor:
+    """The count sketch ``S [rows, cols]`` fp32 of a round delta.  ``a = local - global_`` (one fp32 subtraction);
+    every bucket starts at ``+0.0`` and takes, for the blocks ``q = 0, 1, ..`` in that order, ``+a_i`` or ``-a_i`` of
+    its coordinate ``i`` of block ``q`` (one fp32 addition per block; a coordinate ``i >= n`` adds nothing).  A
+    function of ``(n, rows, cols, seed)`` and the inputs alone.  A non-finite ``a_i`` lands in its ``rows`` buckets."""
+    op = "fedrec_sketch::delta"
+    _check_vec(local, op, "local")
+    _check_vec(global_, op, "global")
+    n, R, C = local.numel(), int(rows), int(cols)
+    if global_.numel() != n:
+        raise RuntimeError(f"{op}: local and global must have one length (got {n}, {global_.numel()})")
+    _sketch_check(op, plan, n, R, C)
+    a = local - global_
+    S = torch.zeros(R, C, dtype=torch.float32)
+    for q in range(plan.shape[0]):
+        i = torch.arange(q * C, min(n, (q + 1) * C), dtype=torch.int64)
+        j, neg = sketch_hash(plan, i, R, C)
+        for r in range(R):
+            S[r, j[r]] = S[r, j[r]] + _flip(a[i], neg[r])
+    return S
+
+
+def order_values(k: torch.Tensor) -> torch.Tensor:
+    """The inverse of :func:`order_keys`; the NaN key 0xFFFFFFFF comes back as the NaN 0x7FFFFFFF."""
+    b = torch.where(k >= 0x80000000, k ^ 0x80000000, _U32 - k)
+    return _wrap_i32(b).view(torch.float32)
+
+
+def sketch_estimate(table: torch.Tensor, plan: torch.Tensor, n: int) -> torch.Tensor:
+    """``est [n]`` fp32 of a sketch ``table [rows, cols]``: ``est_i`` is the median over the rows of ``sign_r(i)
+    table[r, h_r(i)]`` under :func:`order_keys` (``-0.0 < +0.0``, every NaN one key above ``+inf``): the middle of
+    the ``rows`` keys, turned back into its float.  Exact; no tie can show."""
+    op = "fedrec_sketch::estimate"
+    if table.dtype != torch.float32 or table.dim() != 2 or not table.is_contiguous():
+        raise RuntimeError(f"{op}: table must be a contiguous fp32 [rows, cols] tensor")
+    R, C = table.shape
+    _sketch_check(op, plan, int(n), R, C)
+    i = torch.arange(int(n), dtype=torch.int64)
+    j, neg = sketch_hash(plan, i, R, C)
+    keys = torch.stack([order_keys(_flip(table[r, j[r]], neg[r])) for r in range(R)])
+    return order_values(torch.sort(keys, 0).values[R // 2])
+
+
+def sketch_accumulate_(table: torch.Tensor, stack: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+    """In place ``table += (sum over c, in client order, of weights[c] * stack[c]) / sum(weights)``, every element of
+    ``table`` against the same element of ``stack [W, table.numel()]``, ``1 <= W <= 32``; the products, the sums
+    from ``+0.0``, the division and the final addition each rounded on their own (as :func:`dequant_combine`)."""
+    op = "fedrec_sketch::accumulate_"
+    if table.dtype != torch.float32 or not table.is_contiguous():
+        raise RuntimeError(f"{op}: table must be contiguous fp32")
+    if stack.dtype != torch.float32 or stack.dim() != 2 or not stack.is_contiguous() or stack.shape[1] != table.numel():
+        raise RuntimeError(f"{op}: stack must be a contiguous fp32 [W, {table.numel()}] tensor (got {tuple(stack.shape)})")
+    _check_vec(weights, op, "weights")
+    W = stack.shape[0]
+    if not (1 <= W <= 32 and weights.numel() == W):
+        raise RuntimeError(f"{op}: 1 <= W <= 32 and weights [W] (got W {W}, weights {weights.numel()})")
+    acc = torch.zeros(table.numel(), dtype=torch.float32)
+    ws = torch.zeros((), dtype=torch.float32)
+    for c in range(W):
+        acc = acc + weights[c] * stack[c]
+        ws = ws + weights[c]
+    table.copy_((table.reshape(-1) + acc / ws).view_as(table))
+    return table
+
+
+def sketch_clear_(table: torch.Tensor, idx: torch.Tensor, plan: torch.Tensor) -> torch.Tensor:
+    """In place ``table[r, h_r(i)] = +0.0`` for every ``i`` of ``idx`` (int32, inside the plan's blocks; an index
+    outside them is skipped) and every row: idempotent, so members that share a bucket need no order."""
+    op = "fedrec_sketch::clear_"
+    if table.dtype != torch.float32 or table.dim() != 2 or not table.is_contiguous():
+        raise RuntimeError(f"{op}: table must be a contiguous fp32 [rows, cols] tensor")
+    if idx.dtype != torch.int32 or idx.dim() != 1:
+        raise RuntimeError(f"{op}: idx must be int32 [k]")
+    R, C = table.shape
+    _sketch_check(op, plan, plan.shape[0] * C if plan.dim() == 3 and plan.shape[0] else 0, R, C)
+    i = idx.to(torch.int64)
+    i = i[(i >= 0) & (i < plan.shape[0] * C)]
+    j, _ = sketch_hash(plan, i, R, C)
+    for r in range(R):
+        table[r, j[r]] = 0.0
+    return table

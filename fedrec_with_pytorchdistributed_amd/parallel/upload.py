@@ -1,8 +1,8 @@
 """The form of a star client's upload, chosen once per run (:meth:`StarUpload.from_cfg`): the dense fp32 model
 (under the robust rule of parallel/robust.py, when one is set), the top-k list of parallel/sparsify.py, the
-quantised codes of parallel/quantize.py or the low-rank factors of parallel/lowrank.py -- one interface, so that the
-star drivers hold one path for all four.  ``bind(flat_params)``, once after the model is built, gives a codec the
-layout of the flat buffer (only the low-rank one needs it).
+quantised codes of parallel/quantize.py, the low-rank factors of parallel/lowrank.py or the count sketch of
+parallel/sketch.py -- one interface, so that the star drivers hold one path for all five.  ``bind(flat_params)``, once
+after the model is built, gives a codec the layout of the flat buffer (the low-rank and the sketch codec need it).
 
 ``compress(local, theta_g, residual, client, round)`` makes the payload (the flat model, ``(idx, val)``, an ``Upload``),
 ``finite`` tells whether a coordinator may take it, ``pack`` / ``unpack(blob, n)`` are its wire tensor (``unpack``
@@ -27,7 +27,8 @@ class StarUpload:
     uses_residual = True  # the driver keeps an fp32 error-feedback residual (checkpointed as UPLOAD_RESIDUAL)
     options: dict = {}  # the option keys of this form in a round record
     rule = RobustRule()  # (inactive: the dense codec holds the run's)
-    basis = None  # the low-rank codec's per-matrix basis (checkpointed as UPLOAD_BASIS); None on the others
+    # the low-rank codec's per-matrix basis, the sketch codec's error table (checkpointed as UPLOAD_BASIS); None on the others
+    basis = None
 
     @staticmethod
     def from_cfg(cfg, driver: str) -> "StarUpload":
@@ -35,10 +36,14 @@ class StarUpload:
         driver that asks).  Outside the star only the dense codec's ``rule`` means anything."""
         from .lowrank import LowRank  # (StarUploads themselves: both modules import this one)
         from .quantize import Quantizer
+        from .sketch import SketchUpload
         rule = RobustRule.from_cfg(cfg, driver)
         sparse = Sparsifier.from_cfg(cfg, driver)
         quant = Quantizer.from_cfg(cfg, driver)
         low = LowRank.from_cfg(cfg, driver)
+        sketch = SketchUpload.from_cfg(cfg, driver)
+        if sketch.active:
+            return sketch
         if low.active:
             return low
         return quant if quant.active else TopkUpload(sparse) if sparse.active else DenseUpload(rule)
@@ -46,6 +51,13 @@ class StarUpload:
     def bind(self, flat_params) -> "StarUpload":
         """Called once with the model's ``FlatParams``: a codec that needs the layout plans here."""
         return self
+
+    def state(self):
+        """What a coordinator's snapshot keeps of this codec between the rounds (a dict for its extras), or None."""
+        return None
+
+    def load(self, st) -> None:
+        """Take back what :meth:`state` gave (``st``: the snapshot's extras)."""
 
     def check_clients(self, W: int) -> None:
         """``ValueError`` where ``W`` payloads are too few to combine."""

@@ -63,8 +63,8 @@ def save_snapshot(path: str, model: FedRecModel, epoch: int, *, round_idx: Optio
     """``engine``: the engine's own counters (Philox offsets of LDP noise / dropout, sampler
     epoch) so a resumed run draws fresh randomness instead of replaying the saved one.
     ``server_opt``: the server-side step's state (train/federated.py ServerStep), if any.
-    ``extras``: further coordinator state of plain numbers and lists (the client-level DP accountant's
-    history, parallel/cdp.py), if any."""
+    ``extras``: further coordinator state of plain numbers, lists and tensors (the client-level DP accountant's
+    history, parallel/cdp.py; the sketch codec's error table, parallel/sketch.py), if any."""
     snap: Dict[str, Any] = {"MODEL_STATE": cpu_state_dict(model), "EPOCHS_RUN": int(epoch),
                             "NEXT_EPOCH": int(epoch) + 1}
     if server_opt:
@@ -115,7 +115,8 @@ def save_client_state(path: str, model: FedRecModel, round_idx: int, engine: Dic
     client's own seed / checkpoint restore that).  ~14 MB instead of a 270 MB state_dict.
     ``residual``: the error-feedback residual of sparsified uploads (``cfg.upload_topk``), stored
     under ``UPLOAD_RESIDUAL``; without it the snapshot has no such key.  ``basis``: the per-matrix basis of
-    low-rank uploads (``cfg.upload_rank``), under ``UPLOAD_BASIS`` in the same way."""
+    low-rank uploads (``cfg.upload_rank``) or the error table of sketched ones (``cfg.upload_sketch``), under
+    ``UPLOAD_BASIS`` in the same way."""
     snap: Dict[str, Any] = {"FLAT_PARAMS": model.flat.flat.detach().cpu(), "OPTIM_STATE": model.flat.state(),
                             "ROUND": int(round_idx), "ENGINE": {k: int(v) for k, v in engine.items()},
                             "FLAT_NAMES": list(model.flat.names)}

@@ -24,7 +24,8 @@ all-gathers, and the records gain ``dropped_share`` (how often each client's val
 What a star client uploads is the run's codec (parallel/upload.py, ``StarUpload.from_cfg``): the dense model, with
 ``cfg.upload_topk`` the largest-magnitude fraction of its round delta, with ``cfg.upload_bits`` stochastic 8- or 4-bit
 codes of it, with ``cfg.upload_rank`` rank-R factors of every matrix of it (parallel/lowrank.py); what was not sent
-stays in a residual for the next round (error feedback), and the records gain
+stays in a residual for the next round (error feedback); with ``cfg.upload_sketch`` a count sketch of it
+(parallel/sketch.py), where the error feedback is a table on the aggregating side; the records gain
 ``upload_bytes`` / ``dense_bytes``.  A round's tail is secure aggregation or the codec, among the clients
 (``combine_among``) or through the coordinator (``pack`` -> store -> ``unpack`` / ``combine``).
 
@@ -49,7 +50,7 @@ from ..models.fedrec_model import FedRecModel
 from ..parallel import catalog, comm, secagg
 from ..parallel.collcheck import CHECK
 from ..parallel.control import ControlPlane, Heartbeat, encode_tensor
-from ..parallel.upload import StarUpload
+from ..parallel.upload import DenseUpload, StarUpload
 from ..parallel.cdp import ClientDP
 from ..parallel.dist import (DistContext, data_ipc, make_bucket_reducer, make_grad_allreduce, make_secure_grad_allreduce,
                              selfcheck)
@@ -419,7 +420,7 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
                     "zero residual")
         if codec.basis is not None and not info.get("basis_restored"):
             obs.log(f"[client {k}] {csnap} holds no upload basis of {codec.basis.numel()} elements: resuming with the "
-                    "round-1 basis")
+                    "round-1 basis (low-rank) or a zero error table (sketch)")
     beat = Heartbeat(cp, f"client{k}", cfg.heartbeat_s)
     # model sync (server.py:76-77 / client.py:261-264): client 0 alone reads the coordinator's
     # global model from the store and broadcasts it over the client data group (RCCL over
@@ -466,8 +467,8 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
         _receive_global(cp, r, model, ctx, full, bcast)
         _backbone_synced(model, full, before)
         # the round's global model
-        theta_g = (model.flat.flat.detach().clone() if secure is not None or residual is not None or cdp.active
-                   else None)
+        theta_g = (model.flat.flat.detach().clone()
+                   if secure is not None or not isinstance(codec, DenseUpload) or cdp.active else None)
         eng.ensure_cache()  # after the broadcast every client is here: the collective build point
         eng.sigma = _maybe_dp(cfg, eng)
         eng.epoch = 0
@@ -577,6 +578,7 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
         info = ckpt.load_snapshot(cfg.snapshot_path, model)
         server.load(info.get("server_opt"))
         cdp.load(info.get("extras"))
+        codec.load(info.get("extras"))
         start_round = int(info.get("round") or 0) + 1 if info.get("round") is not None else 0
         obs.log(f"[server] resuming at round {start_round}")
     writer = _metrics_writer(cfg, True)
@@ -668,7 +670,8 @@ def run_star_server(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
         obs.log(f"[server] round {r}: {len(accepted)}/{W} clients, {dt:.2f}s, auc={rec.get('valid_auc', float('nan')):.4f}")
         if cfg.snapshot_path:
             ckpt.save_snapshot(cfg.snapshot_path, model, r, round_idx=r, optim=False, config=cfg.to_dict(),
-                               server_opt=server.state(), extras=cdp.state())
+                               server_opt=server.state(),
+                               extras={**(cdp.state() or {}), **(codec.state() or {})})
             gpath = os.path.join(os.path.dirname(os.path.abspath(cfg.snapshot_path)), f"global_model_round{r}.pt")
             ckpt.save_state_dict(gpath, model)
     R = max(cfg.global_rounds, start_round)
