@@ -189,6 +189,10 @@ class FedRecConfig:
     # quantisation with error feedback; ops.quantize_delta / ops.dequant_combine, parallel/quantize.py);
     # with upload_topk the selected values are quantised.  0 = fp32 values
     upload_bits: int = 0
+    # with upload_bits: rotate every 4096 coordinates of the round delta by a randomized Hadamard transform before
+    # they are quantised, keep the residual in the rotated domain and rotate the combined update back once
+    # (ops.rotate_*, parallel/rotate.py): the quantiser's step follows a chunk's norm, not its maximum.  0 = off, 1 = on
+    upload_rotate: int = 0
     # star clients upload every matrix of their round delta as rank-R factors (PowerSGD with error feedback and a
     # warm-started basis; ops.lowrank_*, parallel/lowrank.py), biases and vectors dense; R in {1, 2, 4, 8}, alone
     # among the compressors.  0 = off

@@ -86,7 +86,8 @@ NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 KERNEL_FLAGS = {"krum": NO_PK, "geomed": NO_PK,  # geomed.hip: 16-byte a32 * x + acc, rounded per element
                 "dp_clip": NO_PK,  # dp_clip.hip: 16-byte local - base, base + s * d, p + std * z, rounded per element
                 "lowrank_delta": NO_PK,  # lowrank_delta.hip: 16-byte (local - global) + residual right before its MFMAs
-                "sketch_delta": NO_PK}  # sketch_delta.hip: 16-byte local - global and acc + w * s, rounded per element
+                "sketch_delta": NO_PK,  # sketch_delta.hip: 16-byte local - global and acc + w * s, rounded per element
+                "rotate_delta": NO_PK}  # rotate_delta.hip: butterflies u + v, u - v on 16-byte lines, rounded per element
 
 
 def _clangxx() -> str:

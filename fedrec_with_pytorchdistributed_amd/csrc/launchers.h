@@ -248,6 +248,13 @@ int fr_sketch_estimate(const float* S, const int* plan, float* est, long n, int 
 int fr_sketch_accumulate(float* E, const float* stack, const float* weights, int W, long L, hipStream_t s);
 int fr_sketch_clear(float* E, const int* idx, const int* plan, long k, int nb, int R, long C, hipStream_t s);
 
+// ---- rotate_delta.hip ------------------------------------------------------------------------
+int fr_rotate(const float* x, float* out, long n, int inverse, unsigned long long seed, hipStream_t s);
+int fr_rotate_quantize(const float* local, const float* global, float* residual, unsigned char* codes, float* scales,
+                       long n, int bits, unsigned long long seed, unsigned long long offset, hipStream_t s);
+int fr_rotate_combine(const float* base, const unsigned char* codes, const float* scales, const float* weights,
+                      float* out, int W, long n, int bits, unsigned long long seed, hipStream_t s);
+
 // ---- secagg.hip ------------------------------------------------------------------------------
 int fr_secagg_mask(const float* x, int* out, long n, float scale, float clipv, const unsigned long long* seeds,
                    const int* signs, int npeers, unsigned long long round, hipStream_t s);

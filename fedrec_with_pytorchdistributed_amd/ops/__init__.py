@@ -64,6 +64,9 @@ sketch_estimate /                                  under a block-permutation has
 sketch_accumulate_ /                               one coordinate per block from an LDS ring in block order (no
 sketch_clear_                                      atomics); the median-of-rows estimate from table tiles in LDS;
                                                    W tables added onto the error table; recovered buckets zeroed
+rotate /              (beyond the reference)       rotate_delta.hip: a randomized Hadamard transform per 4096
+rotate_quantize /                                  coordinates (registers, DPP, permlane swaps, one LDS exchange)
+rotate_combine                                     fused in front of the block quantiser and behind its combine
 ====================  ===========================  ===========================================
 """
 from __future__ import annotations
@@ -791,3 +794,35 @@ def sketch_clear_(table, idx, plan):
         torch.ops.fedrec_sketch.clear_(table, idx, plan)
         return table
     return ref.sketch_clear_(table, idx, plan)
+
+
+# Randomized-Hadamard rotation of quantised uploads: csrc/rotate_delta.hip.  ``n_pad = 4096 ceil(n / 4096)``.
+def rotate(x, seed: int, inverse: bool = False, n: Optional[int] = None):
+    """``R x`` per chunk of 4096 coordinates, ``R = 2^-6 H D`` orthonormal (a fast Walsh-Hadamard transform behind the
+    random signs of ``seed``): ``x [n]`` fp32 contiguous -> ``[n_pad]``, or with ``inverse`` ``x [n_pad]`` -> ``[n]``.
+    The exact contract: :func:`ops.reference.rotate`."""
+    if _dev(x):
+        native.require_for(x)
+        return torch.ops.fedrec_rotate.rotate(x, int(seed), bool(inverse), int(n or 0))
+    return ref.rotate(x, int(seed), bool(inverse), n)
+
+
+def rotate_quantize(local, global_, residual_rot, bits: int, seed: int, offset: int):
+    """:func:`quantize_delta` of the rotated round delta in one launch -> ``(codes uint8 [n_pad bits / 8], scales fp32
+    [n_pad / 256])``: bitwise ``quantize_delta(rotate(local - global_), 0, residual_rot, ...)``; ``residual_rot
+    [n_pad]``, the error feedback in the rotated domain, is updated in place and the rotated delta never reaches memory.
+    The exact contract: :func:`ops.reference.rotate_quantize`."""
+    if _dev(residual_rot):
+        native.require_for(residual_rot)
+        return tuple(torch.ops.fedrec_rotate.quantize(local, global_, residual_rot, int(bits), int(seed), int(offset)))
+    return ref.rotate_quantize(local, global_, residual_rot, int(bits), int(seed), int(offset))
+
+
+def rotate_combine(base, codes, scales, weights, bits: int, seed: int):
+    """``W`` rotated uploads applied to ``base [n]`` -> ``out [n]``: the weighted mean of the dequantised codes as
+    :func:`dequant_combine` rounds it, over ``n_pad`` rotated coordinates, rotated back once and added to ``base``.
+    ``codes [W, n_pad bits / 8]``, ``scales [W, n_pad / 256]``.  The exact contract: :func:`ops.reference.rotate_combine`."""
+    if _dev(base):
+        native.require_for(base)
+        return torch.ops.fedrec_rotate.combine(base, codes, scales, weights, int(bits), int(seed))
+    return ref.rotate_combine(base, codes, scales, weights, int(bits), int(seed))

@@ -1164,6 +1164,75 @@ def quant_upload_check(codes: torch.Tensor, scales: torch.Tensor, n: int, bits: 
 
 
 # ---------------------------------------------------------------------------------------
+# Randomized-Hadamard rotation in front of the block quantiser (oracle of csrc/rotate_delta.hip)
+# ---------------------------------------------------------------------------------------
+ROTATE_L = 4096  # coordinates per chunk: 2^12, twelve butterfly stages
+ROTATE_STREAM = 1 << 62  # the Philox offset of the signs: no (client << 32) | round of the quantiser's stream
+
+
+def rotate_pad(n: int) -> int:
+    """``n_pad``: ``n`` rounded up to whole chunks."""
+    return -(-int(n) // ROTATE_L) * ROTATE_L
+
+
+def rotate_signs(n_pad: int, seed: int) -> torch.Tensor:
+    """``d [n_pad]`` fp32, ``-1.0`` where bit 31 of component ``i & 3`` of ``philox4x32(seed, 2^62, i >> 2)`` is set,
+    else ``1.0``: the same on every client and in every round."""
+    words = philox4x32(seed, ROTATE_STREAM, torch.arange(n_pad // 4)).reshape(-1)
+    return torch.where((words >> 31) == 1, -1.0, 1.0).to(torch.float32)
+
+
+def rotate(x: torch.Tensor, seed: int, inverse: bool = False, n: Optional[int] = None) -> torch.Tensor:
+    """``R x`` per chunk of 4096 coordinates, ``R = 2^-6 H D`` (``H`` the Sylvester Hadamard matrix, ``D`` the signs of
+    :func:`rotate_signs`).  Forward: ``x [n]`` -> ``[n_pad]``, the last chunk padded with ``+0.0``; ``t = d x`` (exact),
+    then stages ``s = 0 .. 11`` in that order, every pair ``(p, p | 2^s)`` with bit ``s`` of ``p`` clear ``(u, v) -> (u +
+    v, u - v)``, one fp32 rounding each, then one multiplication by ``2^-6``.  Inverse: ``x [n_pad]`` -> ``[n]`` (``n``:
+    all of it when None): the same stages and scale, then the signs."""
+    _check_vec(x, "fedrec_rotate::rotate", "x")
+    m = x.numel()
+    if inverse and (m == 0 or m % ROTATE_L or rotate_pad(m if n is None else n) != m):
+        raise RuntimeError(f"fedrec_rotate::rotate: the inverse takes the whole chunks of 4096 that n pads to (got {m} for n {n})")
+    n_pad = rotate_pad(m)
+    d = rotate_signs(n_pad, seed).to(x.device)
+    t = F.pad(x, (0, n_pad - m))
+    if not inverse:
+        t = d * t
+    for s in range(12):
+        v = t.view(-1, 2, 1 << s)
+        a, b = v[:, 0], v[:, 1]
+        t = torch.stack([a + b, a - b], 1).reshape(-1)
+    t = t * 2.0 ** -6
+    return (d * t)[:m if n is None else int(n)] if inverse else t
+
+
+def rotate_quantize(local: torch.Tensor, global_: torch.Tensor, residual_rot: torch.Tensor, bits: int, seed: int,
+                    offset: int):
+    """:func:`quantize_delta` of ``z = rotate(local - global_)`` (one fp32 subtraction) against a zero vector ->
+    ``(codes uint8 [n_pad bits / 8], scales fp32 [n_pad / 256])``; ``residual_rot [n_pad]``, the error feedback in the
+    rotated domain, is updated in place.  An inf or a NaN reaches the 16 scale blocks of its chunk."""
+    z = rotate((local - global_).contiguous(), seed)
+    return quantize_delta(z, torch.zeros_like(z), residual_rot, bits, seed, offset)
+
+
+def rotate_combine(base: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, weights: torch.Tensor, bits: int,
+                   seed: int) -> torch.Tensor:
+    """``W`` rotated uploads applied to ``base [n]`` -> ``out [n]``: per rotated coordinate ``acc`` and ``wsum`` as
+    :func:`dequant_combine` forms them over ``n_pad`` coordinates, ``m = acc / wsum``, ``out = base + rotate(m,
+    inverse)[:n]``: averaged in the rotated domain, rotated back once."""
+    bits, n = int(bits), base.numel()
+    n_pad = rotate_pad(n)
+    dequant_combine_check(torch.zeros(n_pad, device=base.device), codes, scales, weights, bits)
+    _check_vec(base, "fedrec_rotate::combine", "base")
+    acc = torch.zeros(n_pad, dtype=torch.float32, device=base.device)
+    ws = torch.zeros((), dtype=torch.float32)
+    for c in range(codes.shape[0]):
+        q = unpack_codes(codes[c], bits, n_pad).to(torch.float32)
+        acc = acc + weights[c] * (q * scales[c].repeat_interleave(QUANT_GROUP))
+        ws = ws + weights[c]
+    return base + rotate(acc / ws, seed, inverse=True, n=n)
+
+
+# ---------------------------------------------------------------------------------------
 # Low-rank (PowerSGD) uploads with error feedback (oracle of csrc/lowrank_delta.hip)
 # ---------------------------------------------------------------------------------------
 LOWRANK_RANKS = (1, 2, 4, 8)

@@ -1,7 +1,7 @@
 """The form of a star client's upload, chosen once per run (:meth:`StarUpload.from_cfg`): the dense fp32 model
 (under the robust rule of parallel/robust.py, when one is set), the top-k list of parallel/sparsify.py, the
-quantised codes of parallel/quantize.py, the low-rank factors of parallel/lowrank.py or the count sketch of
-parallel/sketch.py -- one interface, so that the star drivers hold one path for all five.  ``bind(flat_params)``, once
+quantised codes of parallel/quantize.py (of the rotated delta: parallel/rotate.py), the low-rank factors of
+parallel/lowrank.py or the count sketch of parallel/sketch.py -- one interface, so that the star drivers hold one path for all five.  ``bind(flat_params)``, once
 after the model is built, gives a codec the layout of the flat buffer (the low-rank and the sketch codec need it).
 
 ``compress(local, theta_g, residual, client, round)`` makes the payload (the flat model, ``(idx, val)``, an ``Upload``),
@@ -27,7 +27,8 @@ class StarUpload:
     uses_residual = True  # the driver keeps an fp32 error-feedback residual (checkpointed as UPLOAD_RESIDUAL)
     options: dict = {}  # the option keys of this form in a round record
     rule = RobustRule()  # (inactive: the dense codec holds the run's)
-    # the low-rank codec's per-matrix basis, the sketch codec's error table (checkpointed as UPLOAD_BASIS); None on the others
+    # the low-rank codec's per-matrix basis, the sketch codec's error table, the rotated quantiser's residual
+    # (checkpointed as UPLOAD_BASIS); None on the others
     basis = None
 
     @staticmethod
@@ -36,16 +37,20 @@ class StarUpload:
         driver that asks).  Outside the star only the dense codec's ``rule`` means anything."""
         from .lowrank import LowRank  # (StarUploads themselves: both modules import this one)
         from .quantize import Quantizer
+        from .rotate import RotatedQuantizer
         from .sketch import SketchUpload
         rule = RobustRule.from_cfg(cfg, driver)
         sparse = Sparsifier.from_cfg(cfg, driver)
         quant = Quantizer.from_cfg(cfg, driver)
+        rot = RotatedQuantizer.from_cfg(cfg, driver)
         low = LowRank.from_cfg(cfg, driver)
         sketch = SketchUpload.from_cfg(cfg, driver)
         if sketch.active:
             return sketch
         if low.active:
             return low
+        if rot.active:
+            return rot
         return quant if quant.active else TopkUpload(sparse) if sparse.active else DenseUpload(rule)
 
     def bind(self, flat_params) -> "StarUpload":

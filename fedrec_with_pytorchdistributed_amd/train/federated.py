@@ -420,7 +420,7 @@ def run_star_client(cfg: FedRecConfig, ctx: DistContext, run_id: str = "star") -
                     "zero residual")
         if codec.basis is not None and not info.get("basis_restored"):
             obs.log(f"[client {k}] {csnap} holds no upload basis of {codec.basis.numel()} elements: resuming with the "
-                    "round-1 basis (low-rank) or a zero error table (sketch)")
+                    "round-1 basis (low-rank), a zero error table (sketch) or a zero residual (rotated)")
     beat = Heartbeat(cp, f"client{k}", cfg.heartbeat_s)
     # model sync (server.py:76-77 / client.py:261-264): client 0 alone reads the coordinator's
     # global model from the store and broadcasts it over the client data group (RCCL over
