@@ -193,6 +193,11 @@ class FedRecConfig:
     # they are quantised, keep the residual in the rotated domain and rotate the combined update back once
     # (ops.rotate_*, parallel/rotate.py): the quantiser's step follows a chunk's norm, not its maximum.  0 = off, 1 = on
     upload_rotate: int = 0
+    # star clients upload the sign of every coordinate of their round delta and one fp32 mean magnitude per 256
+    # coordinates (n / 8 + n / 64 bytes) and keep a - copysign(scale, a) as a residual (scaled sign with error
+    # feedback; ops.sign_*, parallel/sign.py).  Instead of upload_bits; with upload_topk the selected values are
+    # sign-coded (STC), with upload_rotate the rotated delta is (DRIVE).  0 = off, 1 = on
+    upload_sign: int = 0
     # star clients upload every matrix of their round delta as rank-R factors (PowerSGD with error feedback and a
     # warm-started basis; ops.lowrank_*, parallel/lowrank.py), biases and vectors dense; R in {1, 2, 4, 8}, alone
     # among the compressors.  0 = off

@@ -87,7 +87,8 @@ KERNEL_FLAGS = {"krum": NO_PK, "geomed": NO_PK,  # geomed.hip: 16-byte a32 * x +
                 "dp_clip": NO_PK,  # dp_clip.hip: 16-byte local - base, base + s * d, p + std * z, rounded per element
                 "lowrank_delta": NO_PK,  # lowrank_delta.hip: 16-byte (local - global) + residual right before its MFMAs
                 "sketch_delta": NO_PK,  # sketch_delta.hip: 16-byte local - global and acc + w * s, rounded per element
-                "rotate_delta": NO_PK}  # rotate_delta.hip: butterflies u + v, u - v on 16-byte lines, rounded per element
+                "rotate_delta": NO_PK,  # rotate_delta.hip: butterflies u + v, u - v on 16-byte lines, rounded per element
+                "sign_delta": NO_PK}  # sign_delta.hip: 16-byte (local - global) + residual and a - copysign(s, a), per element
 
 
 def _clangxx() -> str:

@@ -254,6 +254,16 @@ int fr_rotate_quantize(const float* local, const float* global, float* residual,
                        long n, int bits, unsigned long long seed, unsigned long long offset, hipStream_t s);
 int fr_rotate_combine(const float* base, const unsigned char* codes, const float* scales, const float* weights,
                       float* out, int W, long n, int bits, unsigned long long seed, hipStream_t s);
+int fr_rotate_sign_quantize(const float* local, const float* global, float* residual, unsigned char* codes,
+                            float* scales, long n, unsigned long long seed, hipStream_t s);
+int fr_rotate_sign_combine(const float* base, const unsigned char* codes, const float* scales, const float* weights,
+                           float* out, int W, long n, unsigned long long seed, hipStream_t s);
+
+// ---- sign_delta.hip --------------------------------------------------------------------------
+int fr_sign_quantize(const float* local, const float* global, float* residual, unsigned char* codes, float* scales,
+                     long n, hipStream_t s);
+int fr_sign_combine(const float* base, const unsigned char* codes, const float* scales, const float* weights, float* out,
+                    int W, long n, hipStream_t s);
 
 // ---- secagg.hip ------------------------------------------------------------------------------
 int fr_secagg_mask(const float* x, int* out, long n, float scale, float clipv, const unsigned long long* seeds,

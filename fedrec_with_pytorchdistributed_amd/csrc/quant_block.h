@@ -1,5 +1,6 @@
 // The block quantiser on a lane's registers, shared by quant_delta.hip and rotate_delta.hip: a lane owns 16
-// consecutive coordinates, 16 lanes one scale block of 256.  The contract is the header of quant_delta.hip.
+// consecutive coordinates, 16 lanes one scale block of 256.  The contract is the header of quant_delta.hip.  The lane
+// moves (load16 / store16 / lane_xor) also serve the scaled-sign coder of sign_block.h.
 #pragma once
 #include "common.h"
 
@@ -37,6 +38,27 @@ __device__ __forceinline__ void store16(float* __restrict__ p, uint32_t i0, uint
     for (int e = 0; e < 16; ++e)
       if (i0 + e < n) p[i0 + e] = x[e];
   }
+}
+
+// DPP controls (quad_perm [a,b,c,d] = a | b << 2 | c << 4 | d << 6)
+constexpr int DPP_XOR1 = 0xB1;         // quad_perm [1,0,3,2]
+constexpr int DPP_XOR2 = 0x4E;         // quad_perm [2,3,0,1]
+constexpr int DPP_XOR3 = 0x1B;         // quad_perm [3,2,1,0]
+constexpr int DPP_HALF_MIRROR = 0x141; // row_half_mirror: lane ^ 7 within 8
+constexpr int DPP_ROR8 = 0x128;        // row_ror:8: lane ^ 8 within 16
+
+template <int CTRL>
+__device__ __forceinline__ float dpp(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
+}
+
+// the value of lane ^ M, M in {1, 2, 4, 8}
+template <int M>
+__device__ __forceinline__ float lane_xor(float v) {
+  if (M == 1) return dpp<DPP_XOR1>(v);
+  if (M == 2) return dpp<DPP_XOR2>(v);
+  if (M == 4) return dpp<DPP_HALF_MIRROR>(dpp<DPP_XOR3>(v));
+  return dpp<DPP_ROR8>(v);
 }
 
 // a[16]: the lane's values at coordinates i0 .. i0 + 15 of the scale block that starts at b0 (0.0 past n).  The block

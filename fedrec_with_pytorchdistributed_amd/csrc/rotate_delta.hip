@@ -37,35 +37,19 @@
 // tail chunk, and every chunk when a pointer is not 16-byte aligned (a view such as x[1:]), loads and stores element
 // by element with the same arithmetic in between.  quantize reads 8 n + 4 n_pad bytes and writes 4 n_pad + n_pad
 // bits / 8 + n_pad / 64; combine reads W (n_pad bits / 8 + n_pad / 64) + 4 n and writes 4 n.
+//
+// rotate_sign_quantize / rotate_sign_combine are the same two fused kernels with the scaled-sign coder of sign_delta.hip
+// (sign_block.h) in place of the quantiser, one bit per rotated coordinate: DRIVE.  The rotation is what makes one bit
+// work on a heavy-tailed delta, where the mean magnitude of a block is far below its rms.
 #include "launchers.h"
-#include "quant_block.h"  // load16 / store16 / quantize_store16 / decode_sum16; fp contract(off) from here on
+#include "quant_block.h"  // load16 / store16 / lane_xor / quantize_store16 / decode_sum16; fp contract(off) from here on
+#include "sign_block.h"   // sign_store16 / sign_decode_sum16: the 1-bit coder of sign_delta.hip on the same registers
 
 namespace {
 
 constexpr int BLOCK = 256;
 constexpr uint32_t CHUNK = 4096;
 constexpr uint64_t SIGN_STREAM = 1ull << 62;
-
-// DPP controls (quad_perm [a,b,c,d] = a | b << 2 | c << 4 | d << 6)
-constexpr int DPP_XOR1 = 0xB1;         // quad_perm [1,0,3,2]
-constexpr int DPP_XOR2 = 0x4E;         // quad_perm [2,3,0,1]
-constexpr int DPP_XOR3 = 0x1B;         // quad_perm [3,2,1,0]
-constexpr int DPP_HALF_MIRROR = 0x141; // row_half_mirror: lane ^ 7 within 8
-constexpr int DPP_ROR8 = 0x128;        // row_ror:8: lane ^ 8 within 16
-
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-
-// the value of lane ^ M, M in {1, 2, 4, 8}
-template <int M>
-__device__ __forceinline__ float lane_xor(float v) {
-  if (M == 1) return dpp<DPP_XOR1>(v);
-  if (M == 2) return dpp<DPP_XOR2>(v);
-  if (M == 4) return dpp<DPP_HALF_MIRROR>(dpp<DPP_XOR3>(v));
-  return dpp<DPP_ROR8>(v);
-}
 
 // one stage across lane bit M: own + partner where the bit is clear, partner - own (= partner + (-own), exact) where set
 template <int M>
@@ -213,6 +197,62 @@ __global__ __launch_bounds__(BLOCK) void rotate_combine_kernel(const float* __re
   store16(out, i0, n, fast, o);
 }
 
+// rotate_quantize_kernel with the scaled-sign coder of sign_block.h behind the transform (DRIVE): sign_delta.hip's
+// contract on a = z + residual over n_pad coordinates, every block full
+__global__ __launch_bounds__(BLOCK) void rotate_sign_quantize_kernel(const float* __restrict__ local,
+                                                                    const float* __restrict__ global,
+                                                                    float* __restrict__ residual,
+                                                                    uint8_t* __restrict__ codes, float* __restrict__ scales,
+                                                                    uint32_t n, uint32_t n_pad, uint64_t seed, int vec_in,
+                                                                    int vec_out) {
+  __shared__ __attribute__((aligned(16))) float xch[CHUNK];
+  const int lane = lane_id();
+  const uint32_t i0 = blockIdx.x * CHUNK + threadIdx.x * 16u;
+  const uint32_t b0 = i0 & ~(QB_GROUP - 1);
+  float a[16];
+  {
+    float l[16], g[16];
+    const bool fast = vec_in && i0 + 16 <= n;
+    load16(local, i0, n, fast, l);
+    load16(global, i0, n, fast, g);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) a[e] = l[e] - g[e];
+  }
+  flip_signs(a, i0, seed);
+  fwht_chunk(a, xch);
+  {
+    float r[16];
+    load16(residual, i0, n_pad, vec_out, r);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) a[e] = a[e] + r[e];
+  }
+  sign_store16(a, i0, b0, n_pad, vec_out, lane, residual, codes, scales);
+}
+
+// rotate_combine_kernel over sign codes: codes [W, n_pad / 8], scales [W, n_pad / 256]; vec: base and out 16-byte aligned
+__global__ __launch_bounds__(BLOCK) void rotate_sign_combine_kernel(const float* __restrict__ base,
+                                                                   const uint8_t* __restrict__ codes,
+                                                                   const float* __restrict__ scales,
+                                                                   const float* __restrict__ wts, float* __restrict__ out,
+                                                                   int W, uint32_t n, uint32_t n_pad, uint64_t seed,
+                                                                   int vec) {
+  __shared__ __attribute__((aligned(16))) float xch[CHUNK];
+  const uint32_t i0 = blockIdx.x * CHUNK + threadIdx.x * 16u;
+  float m[16], ws;
+  sign_decode_sum16(codes, scales, wts, W, (size_t)n_pad >> 3, n_pad / QB_GROUP, i0, i0 / QB_GROUP, n_pad, true, m, ws);
+#pragma unroll
+  for (int e = 0; e < 16; ++e) m[e] = m[e] / ws;
+  fwht_chunk(m, xch);
+  flip_signs(m, i0, seed);
+  if (i0 >= n) return;  // (behind the last barrier)
+  const bool fast = vec && i0 + 16 <= n;
+  float o[16];
+  load16(base, i0, n, fast, o);
+#pragma unroll
+  for (int e = 0; e < 16; ++e) o[e] = o[e] + m[e];
+  store16(out, i0, n, fast, o);
+}
+
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 inline long pad_of(long n) { return (n + CHUNK - 1) / CHUNK * CHUNK; }
 inline bool bad_n(long n) { return n < 1 || n > (1L << 31) - CHUNK; }  // n_pad < 2^31
@@ -268,5 +308,32 @@ extern "C" int fr_rotate_combine(const float* base, const unsigned char* codes, 
   else
     hipLaunchKernelGGL(rotate_combine_kernel<4>, grid, blk, 0, s, base, codes, scales, weights, out, W, (uint32_t)n,
                        (uint32_t)n_pad, (uint64_t)seed, vec);
+  return hipGetLastError() == hipSuccess ? 0 : 3;
+}
+
+// fr_rotate_quantize with the scaled-sign coder: codes [n_pad / 8].  1: a shape outside 1 <= n <= 2^31 - 4096; 2: a
+// float pointer that is not 4-byte aligned; 3: a runtime error
+extern "C" int fr_rotate_sign_quantize(const float* local, const float* global, float* residual, unsigned char* codes,
+                                       float* scales, long n, unsigned long long seed, hipStream_t s) {
+  if (bad_n(n)) return 1;
+  if (((uintptr_t)local | (uintptr_t)global | (uintptr_t)residual | (uintptr_t)scales) & 3u) return 2;
+  const long n_pad = pad_of(n);
+  const int vec_in = aligned16(local) && aligned16(global), vec_out = aligned16(residual) && aligned16(codes);
+  hipLaunchKernelGGL(rotate_sign_quantize_kernel, dim3((unsigned)(n_pad / CHUNK)), dim3(BLOCK), 0, s, local, global,
+                     residual, codes, scales, (uint32_t)n, (uint32_t)n_pad, (uint64_t)seed, vec_in, vec_out);
+  return hipGetLastError() == hipSuccess ? 0 : 3;
+}
+
+// fr_rotate_combine over sign codes: codes [W, n_pad / 8].  1: a shape outside 1 <= W <= 65536, 1 <= n <= 2^31 - 4096;
+// 2: a float pointer that is not 4-byte aligned; 3: a runtime error
+extern "C" int fr_rotate_sign_combine(const float* base, const unsigned char* codes, const float* scales,
+                                      const float* weights, float* out, int W, long n, unsigned long long seed,
+                                      hipStream_t s) {
+  if (W < 1 || W > 65536 || bad_n(n)) return 1;
+  if (((uintptr_t)base | (uintptr_t)scales | (uintptr_t)weights | (uintptr_t)out) & 3u) return 2;
+  const long n_pad = pad_of(n);
+  const int vec = aligned16(base) && aligned16(out);
+  hipLaunchKernelGGL(rotate_sign_combine_kernel, dim3((unsigned)(n_pad / CHUNK)), dim3(BLOCK), 0, s, base, codes, scales,
+                     weights, out, W, (uint32_t)n, (uint32_t)n_pad, (uint64_t)seed, vec);
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }

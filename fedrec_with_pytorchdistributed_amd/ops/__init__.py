@@ -67,6 +67,10 @@ sketch_clear_                                      atomics); the median-of-rows 
 rotate /              (beyond the reference)       rotate_delta.hip: a randomized Hadamard transform per 4096
 rotate_quantize /                                  coordinates (registers, DPP, permlane swaps, one LDS exchange)
 rotate_combine                                     fused in front of the block quantiser and behind its combine
+sign_quantize /       (beyond the reference)       sign_delta.hip: one sign bit per coordinate and one mean
+sign_combine /                                     magnitude per 256 with the error-feedback residual (run sums
+rotate_sign_quantize /                             in the lane, DPP butterflies, a wave stores 128 contiguous bytes
+rotate_sign_combine                                of bits); rotate_delta.hip: the same coder behind the transform
 ====================  ===========================  ===========================================
 """
 from __future__ import annotations
@@ -826,3 +830,55 @@ def rotate_combine(base, codes, scales, weights, bits: int, seed: int):
         native.require_for(base)
         return torch.ops.fedrec_rotate.combine(base, codes, scales, weights, int(bits), int(seed))
     return ref.rotate_combine(base, codes, scales, weights, int(bits), int(seed))
+
+
+# 1-bit scaled-sign uploads: csrc/sign_delta.hip, and behind the rotation csrc/rotate_delta.hip.
+def sign_quantize(local, global_, residual):
+    """Scaled-sign coding of a round delta with error feedback -> ``(codes uint8 [ceil(n / 8)], scales fp32 [ceil(n /
+    256)])``; ``residual`` is updated in place.  ``local``, ``global_``, ``residual`` ``[n]`` fp32 contiguous (a view such
+    as ``x[1:]`` is fine), ``residual`` overlapping neither input, ``1 <= n < 2^31``.  ``a = (local - global_) +
+    residual``; each block of 256 coordinates gets its mean magnitude as the scale and every coordinate its sign bit;
+    ``residual`` becomes ``a - copysign(scale, a)``.  A block with an inf or a NaN sends a NaN scale, zero codes and
+    keeps a zero residual.  Deterministic, bitwise independent of the grid.  The exact contract:
+    :func:`ops.reference.sign_quantize`."""
+    if _dev(residual):
+        native.require_for(residual)
+        return tuple(torch.ops.fedrec_sign.quantize(local, global_, residual))
+    return ref.sign_quantize(local, global_, residual)
+
+
+def sign_combine(base, codes, scales, weights):
+    """``W`` sign uploads applied to ``base [n]`` fp32 -> ``out [n]``: ``out = base + (sum over c, in client order, of
+    +-(weights[c] * scale[c])) / sum(weights)``.  ``codes [W, ceil(n / 8)]`` uint8, ``scales [W, ceil(n / 256)]`` fp32
+    (callers validate with :func:`ops.reference.quant_upload_check`; the kernel stays in bounds whatever the content),
+    ``weights [W]`` fp32.  The exact contract: :func:`ops.reference.sign_combine`."""
+    if _dev(base):
+        native.require_for(base)
+        return torch.ops.fedrec_sign.combine(base, codes, scales, weights)
+    return ref.sign_combine(base, codes, scales, weights)
+
+
+def sign_dequantize(codes, scales, n: int):
+    """One upload's delta ``[n]`` fp32: :func:`sign_combine` with ``W = 1``, a zero base and weight 1."""
+    return sign_combine(torch.zeros(int(n), dtype=torch.float32, device=codes.device), codes.reshape(1, -1),
+                        scales.reshape(1, -1), torch.ones(1, dtype=torch.float32, device=codes.device))
+
+
+def rotate_sign_quantize(local, global_, residual_rot, seed: int):
+    """:func:`sign_quantize`'s coder on the rotated round delta in one launch -> ``(codes uint8 [n_pad / 8], scales fp32
+    [n_pad / 256])``; ``residual_rot [n_pad]``, the error feedback in the rotated domain, is updated in place and the
+    rotated delta never reaches memory.  The exact contract: :func:`ops.reference.rotate_sign_quantize`."""
+    if _dev(residual_rot):
+        native.require_for(residual_rot)
+        return tuple(torch.ops.fedrec_sign.rotate_quantize(local, global_, residual_rot, int(seed)))
+    return ref.rotate_sign_quantize(local, global_, residual_rot, int(seed))
+
+
+def rotate_sign_combine(base, codes, scales, weights, seed: int):
+    """``W`` rotated sign uploads applied to ``base [n]`` -> ``out [n]``: :func:`sign_combine`'s weighted mean over
+    ``n_pad`` rotated coordinates, rotated back once and added to ``base``.  ``codes [W, n_pad / 8]``, ``scales [W,
+    n_pad / 256]``.  The exact contract: :func:`ops.reference.rotate_sign_combine`."""
+    if _dev(base):
+        native.require_for(base)
+        return torch.ops.fedrec_sign.rotate_combine(base, codes, scales, weights, int(seed))
+    return ref.rotate_sign_combine(base, codes, scales, weights, int(seed))

@@ -1233,6 +1233,156 @@ def rotate_combine(base: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor
 
 
 # ---------------------------------------------------------------------------------------
+# 1-bit scaled-sign uploads with error feedback (oracle of csrc/sign_delta.hip and the rotate_sign_* kernels)
+# ---------------------------------------------------------------------------------------
+def _sign_quantize_check(op: str, local: torch.Tensor, global_: torch.Tensor, residual: torch.Tensor, rotated: bool) -> int:
+    """The argument checks of ``fedrec_sign::quantize`` / ``rotate_quantize``, with their messages -> the coordinates coded."""
+    rname = "residual_rot" if rotated else "residual"
+    _check_vec(local, op, "local")
+    _check_vec(global_, op, "global")
+    _check_vec(residual, op, rname)
+    n = local.numel()
+    if global_.numel() != n:
+        raise RuntimeError(f"{op}: local and global must have one length (got {n}, {global_.numel()})")
+    m = _sign_coded(op, n, rotated)
+    if residual.numel() != m:
+        raise RuntimeError(f"{op}: {rname} must have {m} coordinates for n {n} (got {residual.numel()})")
+    if not (local.device == residual.device and global_.device == residual.device):
+        raise RuntimeError(f"{op}: local, global and {rname} must be on one device")
+    if _overlaps(residual, local) or _overlaps(residual, global_):
+        raise RuntimeError(f"{op}: {rname} must not overlap local or global")
+    return m
+
+
+def _sign_coded(op: str, n: int, rotated: bool) -> int:
+    if not rotated:
+        if not (1 <= n < 2 ** 31):
+            raise RuntimeError(f"{op}: 1 <= n < 2^31 (got n {n})")
+        return n
+    if not (1 <= n <= 2 ** 31 - ROTATE_L):
+        raise RuntimeError(f"{op}: 1 <= n <= 2^31 - 4096 (got n {n})")
+    return rotate_pad(n)
+
+
+def _sign_combine_check(op: str, base: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, weights: torch.Tensor,
+                        rotated: bool) -> int:
+    """The argument checks of ``fedrec_sign::combine`` / ``rotate_combine``, with their messages -> the coordinates coded."""
+    _check_vec(base, op, "base")
+    if codes.dtype != torch.uint8:
+        raise RuntimeError(f"{op}: codes must be uint8")
+    if scales.dtype != torch.float32:
+        raise RuntimeError(f"{op}: scales must be fp32")
+    if not (codes.dim() == 2 and scales.dim() == 2):
+        raise RuntimeError(f"{op}: codes [W, nbytes] and scales [W, nb]")
+    if not (codes.is_contiguous() and scales.is_contiguous()):
+        raise RuntimeError(f"{op}: codes and scales must be contiguous")
+    _check_vec(weights, op, "weights")
+    n, W = base.numel(), codes.shape[0]
+    m = _sign_coded(op, n, rotated)
+    if not (1 <= W <= 65536 and weights.numel() == W and scales.shape[0] == W):
+        raise RuntimeError(f"{op}: 1 <= W <= 65536, scales [W, nb] and weights [W] (got W {W}, scales {scales.shape[0]}, "
+                           f"weights {weights.numel()})")
+    nbytes, nb = quant_sizes(m, 1)
+    if not (codes.shape[1] == nbytes and scales.shape[1] == nb):
+        raise RuntimeError(f"{op}: n {n} takes codes [W, {nbytes}] and scales [W, {nb}] (got {codes.shape[1]}, "
+                           f"{scales.shape[1]})")
+    if not (codes.device == base.device and scales.device == base.device and weights.device == base.device):
+        raise RuntimeError(f"{op}: base, codes, scales and weights must be on one device")
+    return m
+
+
+def _sign_code(a: torch.Tensor, residual: torch.Tensor):
+    """The coder of :func:`sign_quantize` on ``a [n]``; ``residual [n]`` takes what is kept."""
+    n, G = a.numel(), QUANT_GROUP
+    nbytes, nb = quant_sizes(n, 1)
+    mag = F.pad(a.abs(), (0, nb * G - n)).view(nb, 16, 16)  # block, run, coordinate of the run
+    p = torch.zeros(nb, 16, dtype=torch.float32)
+    for e in range(16):  # each run in ascending order from +0.0
+        p = p + mag[:, :, e]
+    j = torch.arange(16)
+    for o in (1, 2, 4, 8):  # p_j + p_(j ^ o): the same bits in all 16
+        p = p + p[:, j ^ o]
+    p = p[:, 0]
+    count = torch.clamp(n - G * torch.arange(nb), max=G).to(torch.float32)
+    s = p / count
+    nonfinite = (p.view(torch.int32) & 0x7FFFFFFF) >= 0x7F800000
+    live = ~nonfinite & (s >= 2.0 ** -126)
+    zero = torch.zeros((), dtype=torch.float32)
+    scales = torch.where(nonfinite, _canonical_nan(), torch.where(live, s, zero))
+    el = lambda t: t.repeat_interleave(G)[:n]  # noqa: E731  (per block -> per coordinate)
+    live_e = el(live)
+    r = a - torch.copysign(el(s), a)
+    residual.copy_(torch.where(live_e, r, torch.where(el(nonfinite), zero, a)))
+    bit = F.pad(((a.view(torch.int32) < 0) & live_e).to(torch.int64), (0, 8 * nbytes - n)).view(nbytes, 8)
+    return (bit << torch.arange(8)).sum(1).to(torch.uint8), scales
+
+
+def sign_quantize(local: torch.Tensor, global_: torch.Tensor, residual: torch.Tensor):
+    """Scaled-sign coding with error feedback -> ``(codes uint8 [ceil(n / 8)], scales fp32 [ceil(n / 256)])``;
+    ``residual`` is updated in place.  Deterministic: no Philox, no seed.
+
+    ``a = (local - global_) + residual`` (one fp32 subtraction, one fp32 addition).  Per block of 256 coordinates ``p``
+    is the sum of ``|a|`` (``+0.0`` past ``n``) in a fixed order: 16 runs of 16 consecutive coordinates, each summed
+    from ``+0.0`` in ascending order, then four butterfly steps ``p_j = p_j + p_(j ^ o)``, ``o = 1, 2, 4, 8``, over the
+    run sums.  ``s = p / float(min(256, n - b0))``, one division: the block's mean magnitude.  ``bits(p) & 0x7fffffff >=
+    0x7f800000`` (an inf, a NaN, an overflowing sum): the canonical NaN as the scale, zero codes, a ``+0.0`` residual.
+    Else ``s < 2^-126``: a zero block (scale ``+0.0``, zero codes, ``residual = a``).  Else bit ``i & 7`` of byte ``i >>
+    3`` is the sign bit of ``a[i]`` (``-0.0`` codes 1) and ``residual[i] = a[i] - copysign(s, a[i])``.  Padding bits
+    are zero."""
+    _sign_quantize_check("fedrec_sign::quantize", local, global_, residual, False)
+    return _sign_code((local - global_) + residual, residual)
+
+
+def unpack_signs(codes: torch.Tensor, n: int) -> torch.Tensor:
+    """Bit ``i & 7`` of byte ``i >> 3`` over the last dimension -> bool ``[..., n]``."""
+    c = codes.to(torch.int64)
+    return (((c[..., None] >> torch.arange(8, device=codes.device)) & 1) == 1).reshape(*c.shape[:-1], -1)[..., :n]
+
+
+def _sign_mean(codes: torch.Tensor, scales: torch.Tensor, weights: torch.Tensor, m: int) -> torch.Tensor:
+    """``acc / wsum`` of :func:`sign_combine` over ``m`` coded coordinates."""
+    acc = torch.zeros(m, dtype=torch.float32, device=codes.device)
+    ws = torch.zeros((), dtype=torch.float32)
+    for c in range(codes.shape[0]):
+        t = (weights[c] * scales[c]).repeat_interleave(QUANT_GROUP)[:m]
+        acc = acc + torch.where(unpack_signs(codes[c], m), -t, t)
+        ws = ws + weights[c]
+    return acc / ws
+
+
+def sign_combine(base: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+    """``W`` sign uploads applied to ``base [n]`` -> ``out [n]`` fp32.  ``codes [W, ceil(n / 8)]`` uint8, ``scales [W,
+    ceil(n / 256)]`` fp32, ``weights [W]``.  ``acc`` starts at ``+0.0``; for ``c = 0 .. W - 1`` in that order ``t =
+    weights[c] * scales[c, i / 256]`` (one rounding) and ``acc[i] += -t if bit else t``; ``wsum`` is the sequential fp32
+    sum of the weights from ``+0.0``; ``out = base + acc / wsum``.  Rejecting a bad upload is the caller's check
+    (:func:`quant_upload_check` with ``bits = 1``)."""
+    n = _sign_combine_check("fedrec_sign::combine", base, codes, scales, weights, False)
+    return base + _sign_mean(codes, scales, weights, n)
+
+
+def sign_dequantize(codes: torch.Tensor, scales: torch.Tensor, n: int) -> torch.Tensor:
+    """One upload's delta ``d [n]``: :func:`sign_combine` with ``W = 1``, a zero base and weight 1."""
+    return sign_combine(torch.zeros(int(n), dtype=torch.float32, device=codes.device), codes.reshape(1, -1),
+                        scales.reshape(1, -1), torch.ones(1, dtype=torch.float32, device=codes.device))
+
+
+def rotate_sign_quantize(local: torch.Tensor, global_: torch.Tensor, residual_rot: torch.Tensor, seed: int):
+    """:func:`sign_quantize`'s coder on ``a = rotate(local - global_) + residual_rot`` (one fp32 subtraction, one fp32
+    addition) over ``n_pad`` coordinates, every block full -> ``(codes uint8 [n_pad / 8], scales fp32 [n_pad / 256])``;
+    ``residual_rot [n_pad]`` is updated in place.  An inf or a NaN reaches the 16 scale blocks of its chunk."""
+    _sign_quantize_check("fedrec_sign::rotate_quantize", local, global_, residual_rot, True)
+    return _sign_code(rotate((local - global_).contiguous(), seed) + residual_rot, residual_rot)
+
+
+def rotate_sign_combine(base: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, weights: torch.Tensor,
+                        seed: int) -> torch.Tensor:
+    """``W`` rotated sign uploads applied to ``base [n]`` -> ``out [n]``: ``m = acc / wsum`` as :func:`sign_combine`
+    forms it over ``n_pad`` rotated coordinates, ``out = base + rotate(m, inverse)[:n]``."""
+    n_pad = _sign_combine_check("fedrec_sign::rotate_combine", base, codes, scales, weights, True)
+    return base + rotate(_sign_mean(codes, scales, weights, n_pad), seed, inverse=True, n=base.numel())
+
+
+# ---------------------------------------------------------------------------------------
 # Low-rank (PowerSGD) uploads with error feedback (oracle of csrc/lowrank_delta.hip)
 # ---------------------------------------------------------------------------------------
 LOWRANK_RANKS = (1, 2, 4, 8)

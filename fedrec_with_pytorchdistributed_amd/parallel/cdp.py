@@ -64,6 +64,9 @@ class ClientDP:
         if cfg.upload_bits:
             raise ValueError(f"cdp.clip={c.clip} cannot be combined with upload_bits={cfg.upload_bits}: the "
                              "error-feedback residual is unprivatised state")
+        if cfg.upload_sign:
+            raise ValueError(f"cdp.clip={c.clip} cannot be combined with upload_sign={cfg.upload_sign}: the "
+                             "error-feedback residual is unprivatised state")
         if cfg.upload_rank:
             raise ValueError(f"cdp.clip={c.clip} cannot be combined with upload_rank={cfg.upload_rank}: the "
                              "error-feedback residual is unprivatised state")

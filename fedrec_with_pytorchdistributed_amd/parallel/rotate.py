@@ -45,8 +45,10 @@ class RotatedQuantizer(Quantizer):  # (its payload: an Upload over n_pad coordin
         if not rot:
             return cls(0, cfg.seed)
         if not cfg.upload_bits:
-            raise ValueError("upload_rotate=1 needs upload_bits=8 or 4: the rotation prepares the round delta for the "
-                             "block quantiser and does nothing for an fp32 upload")
+            if cfg.upload_sign:  # the rotated sign code: parallel/sign.py owns it
+                return cls(0, cfg.seed)
+            raise ValueError("upload_rotate=1 needs upload_bits=8 or 4, or upload_sign=1: the rotation prepares the round "
+                             "delta for the block quantiser or the sign coder and does nothing for an fp32 upload")
         if cfg.upload_topk:
             raise ValueError(f"upload_rotate=1 cannot be combined with upload_topk={cfg.upload_topk}: the quantiser then "
                              "codes a list of selected values, and list positions are not coordinates to rotate")

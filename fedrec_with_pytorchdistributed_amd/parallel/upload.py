@@ -1,7 +1,7 @@
 """The form of a star client's upload, chosen once per run (:meth:`StarUpload.from_cfg`): the dense fp32 model
 (under the robust rule of parallel/robust.py, when one is set), the top-k list of parallel/sparsify.py, the
-quantised codes of parallel/quantize.py (of the rotated delta: parallel/rotate.py), the low-rank factors of
-parallel/lowrank.py or the count sketch of parallel/sketch.py -- one interface, so that the star drivers hold one path for all five.  ``bind(flat_params)``, once
+quantised codes of parallel/quantize.py (of the rotated delta: parallel/rotate.py), the sign bits of parallel/sign.py, the
+low-rank factors of parallel/lowrank.py or the count sketch of parallel/sketch.py -- one interface, so that the star drivers hold one path for all six.  ``bind(flat_params)``, once
 after the model is built, gives a codec the layout of the flat buffer (the low-rank and the sketch codec need it).
 
 ``compress(local, theta_g, residual, client, round)`` makes the payload (the flat model, ``(idx, val)``, an ``Upload``),
@@ -38,6 +38,7 @@ class StarUpload:
         from .lowrank import LowRank  # (StarUploads themselves: both modules import this one)
         from .quantize import Quantizer
         from .rotate import RotatedQuantizer
+        from .sign import SignUpload
         from .sketch import SketchUpload
         rule = RobustRule.from_cfg(cfg, driver)
         sparse = Sparsifier.from_cfg(cfg, driver)
@@ -45,6 +46,9 @@ class StarUpload:
         rot = RotatedQuantizer.from_cfg(cfg, driver)
         low = LowRank.from_cfg(cfg, driver)
         sketch = SketchUpload.from_cfg(cfg, driver)
+        sign = SignUpload.from_cfg(cfg, driver)
+        if sign.active:
+            return sign
         if sketch.active:
             return sketch
         if low.active:
