@@ -23,7 +23,9 @@ round delta (``8 k`` bytes instead of ``4 n``); ``--upload_bits=8`` / ``--upload
 without ``--upload_topk``) rotates every 4096 coordinates by a randomized Hadamard transform first, so that a few
 large coordinates no longer set the step of the rest; ``--upload_sign=1`` (instead of ``--upload_bits``) sends one sign
 bit per coordinate and one fp32 mean magnitude per 256 (``ceil(n / 8) + 4 ceil(n / 256)`` bytes), of the selected values
-with ``--upload_topk`` and of the rotated delta with ``--upload_rotate=1``.  None of them combines with
+with ``--upload_topk`` and of the rotated delta with ``--upload_rotate=1``; ``--upload_index=ef`` (with ``--upload_topk``,
+alone or with ``--upload_bits`` / ``--upload_sign``) sends the selected positions Elias-Fano coded, about ``log2(n / k) + 2``
+bits each instead of 32, lossless.  None of them combines with
 ``--secagg.enabled=1``, ``--robust_agg`` or the averaging modes.  ``--upload_rank=R`` (1, 2, 4 or 8) sends
 every matrix of the round delta as rank-``R`` factors (``4 R (rows + cols)`` bytes instead of ``4 rows cols``;
 biases and vectors dense) and keeps its basis next to the residual in the client snapshot; it combines with

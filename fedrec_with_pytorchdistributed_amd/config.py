@@ -198,6 +198,10 @@ class FedRecConfig:
     # feedback; ops.sign_*, parallel/sign.py).  Instead of upload_bits; with upload_topk the selected values are
     # sign-coded (STC), with upload_rotate the rotated delta is (DRIVE).  0 = off, 1 = on
     upload_sign: int = 0
+    # how the top-k forms (upload_topk alone, with upload_bits, with upload_sign) send the k selected positions:
+    # raw = one int32 each; ef = Elias-Fano coded, b + 1 + n / (k 2^b) bits each with b = floor(log2(n / k)), lossless
+    # (ops.ef_*, parallel/index_code.py).  raw | ef
+    upload_index: str = "raw"
     # star clients upload every matrix of their round delta as rank-R factors (PowerSGD with error feedback and a
     # warm-started basis; ops.lowrank_*, parallel/lowrank.py), biases and vectors dense; R in {1, 2, 4, 8}, alone
     # among the compressors.  0 = off

@@ -265,6 +265,12 @@ int fr_sign_quantize(const float* local, const float* global, float* residual, u
 int fr_sign_combine(const float* base, const unsigned char* codes, const float* scales, const float* weights, float* out,
                     int W, long n, hipStream_t s);
 
+// ---- index_code.hip --------------------------------------------------------------------------
+int fr_ef_plan(long n, long k, int* b, long* low_words, long* high_bits, long* high_words);
+int fr_ef_encode(const int* idx, int* words, long n, long k, hipStream_t s);
+long fr_ef_decode_ws(long n, long k, int W);  // workspace of fr_ef_decode in 32-bit words
+int fr_ef_decode(const int* words, int* idx, long* count, unsigned* ws, int W, long n, long k, hipStream_t s);
+
 // ---- secagg.hip ------------------------------------------------------------------------------
 int fr_secagg_mask(const float* x, int* out, long n, float scale, float clipv, const unsigned long long* seeds,
                    const int* signs, int npeers, unsigned long long round, hipStream_t s);

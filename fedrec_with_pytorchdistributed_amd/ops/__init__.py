@@ -71,6 +71,9 @@ sign_quantize /       (beyond the reference)       sign_delta.hip: one sign bit 
 sign_combine /                                     magnitude per 256 with the error-feedback residual (run sums
 rotate_sign_quantize /                             in the lane, DPP butterflies, a wave stores 128 contiguous bytes
 rotate_sign_combine                                of bits); rotate_delta.hip: the same coder behind the transform
+ef_encode /           (beyond the reference)       index_code.hip: Elias-Fano coding of a top-k upload's index list
+ef_decode                                          (low fields packed per wave through LDS, the unary high vector by
+                                                   tiles with an LDS OR; the decoder ranks set bits by popcount scans)
 ====================  ===========================  ===========================================
 """
 from __future__ import annotations
@@ -882,3 +885,29 @@ def rotate_sign_combine(base, codes, scales, weights, seed: int):
         native.require_for(base)
         return torch.ops.fedrec_sign.rotate_combine(base, codes, scales, weights, int(seed))
     return ref.rotate_sign_combine(base, codes, scales, weights, int(seed))
+
+
+# Elias-Fano coding of the top-k forms' index list: csrc/index_code.hip.
+def ef_encode(idx, n: int):
+    """``idx`` int32 ``[k]``, strictly ascending in ``[0, n)`` (:func:`topk_delta`'s), ``1 <= k <= n < 2^31`` -> the
+    Elias-Fano words int32 ``[low_words + high_words]`` of :func:`ops.reference.ef_plan`: ``b + 1 + n / (k 2^b)`` bits
+    an index instead of 32, a size that depends on ``(n, k)`` alone, lossless.  One launch on the device, every word
+    written once.  The exact contract: :func:`ops.reference.ef_encode`."""
+    if _dev(idx):
+        native.require_for(idx)
+        return torch.ops.fedrec_index.encode(idx, int(n))
+    return ref.ef_encode(idx, int(n))
+
+
+def ef_decode(words, n: int, k: int):
+    """``W`` blobs ``words [W, low_words + high_words]`` int32 -> ``(idx [W, k] int32, count [W] int64)``.  On the
+    device a row of ANY content is decoded in bounds: ``count`` is its set high bits, ``idx`` holds -1 where a rank has
+    no value in ``[0, n)``, and :func:`ops.reference.ef_decoded_check` tells whether the row is a code.  On the host
+    every row goes through :func:`ops.reference.ef_decode`, which raises ``ValueError`` itself."""
+    if _dev(words):
+        native.require_for(words)
+        return tuple(torch.ops.fedrec_index.decode(words, int(n), int(k)))
+    if words.dim() != 2:
+        raise RuntimeError(f"fedrec_index::decode: words [W, low_words + high_words] (got {words.dim()} dims)")
+    return (torch.stack([ref.ef_decode(row, int(n), int(k)) for row in words]),
+            torch.full((words.shape[0],), int(k), dtype=torch.int64))

@@ -1383,6 +1383,92 @@ def rotate_sign_combine(base: torch.Tensor, codes: torch.Tensor, scales: torch.T
 
 
 # ---------------------------------------------------------------------------------------
+# Elias-Fano coding of the top-k forms' index list (oracle of csrc/index_code.hip)
+# ---------------------------------------------------------------------------------------
+def ef_plan(n: int, k: int) -> Tuple[int, int, int, int]:
+    """``(b, low_words, high_bits, high_words)`` of ``k`` strictly ascending positions in ``[0, n)``, ``1 <= k <= n <
+    2^31``.  ``b`` is the largest integer with ``(k << b) <= n`` (0 when ``k > n / 2``).  The low section holds ``k``
+    fields of ``b`` bits, ``idx_i & (2^b - 1)``, field ``i`` at bit ``i b``, LSB first in little-endian uint32 words:
+    ``low_words = ceil(k b / 32)``.  The high section is a bit vector of ``high_bits = k + ((n - 1) >> b) + 1`` bits
+    (``high_words = ceil(high_bits / 32)``) with bit ``(idx_i >> b) + i`` set for every ``i``.  The blob is the low
+    words, then the high words, as int32; every padding bit is zero.  ``b + 1 + n / (k 2^b)`` bits per index."""
+    n, k = int(n), int(k)
+    if not 1 <= k <= n < 2 ** 31:
+        raise ValueError(f"Elias-Fano index: 1 <= k <= n < 2^31 (got k {k}, n {n})")
+    b = 0
+    while (k << (b + 1)) <= n:
+        b += 1
+    high_bits = k + ((n - 1) >> b) + 1
+    return b, (k * b + 31) // 32, high_bits, (high_bits + 31) // 32
+
+
+def _ef_bits(words: torch.Tensor) -> torch.Tensor:
+    """The bits of int32 words, LSB first, as int64 0 / 1 ``[32 len]``."""
+    return (((words.long() & _U32)[:, None] >> torch.arange(32, device=words.device)) & 1).reshape(-1)
+
+
+def _ef_words(bits: torch.Tensor, nwords: int) -> torch.Tensor:
+    """``bits`` (int64 0 / 1, LSB first), zero-padded to ``nwords`` int32 words."""
+    pad = torch.zeros(32 * nwords, dtype=torch.int64, device=bits.device)
+    pad[:bits.numel()] = bits
+    return _wrap_i32((pad.view(nwords, 32) << torch.arange(32, device=bits.device)).sum(1))
+
+
+def ef_encode(idx: torch.Tensor, n: int) -> torch.Tensor:
+    """``idx`` int32 ``[k]``, strictly ascending in ``[0, n)`` as :func:`topk_delta` gives it (the caller's contract)
+    -> the blob of :func:`ef_plan`, int32 ``[low_words + high_words]``."""
+    if idx.dtype != torch.int32 or idx.dim() != 1:
+        raise RuntimeError(f"fedrec_index::encode: idx must be int32 [k] (got {idx.dtype} {tuple(idx.shape)})")
+    k = idx.numel()
+    b, low_words, high_bits, high_words = ef_plan(n, k)
+    i = idx.long()
+    low = (((i & ((1 << b) - 1))[:, None] >> torch.arange(b, device=idx.device)) & 1).reshape(-1)
+    high = torch.zeros(high_bits, dtype=torch.int64, device=idx.device)
+    high[(i >> b) + torch.arange(k, device=idx.device)] = 1
+    return torch.cat([_ef_words(low, low_words), _ef_words(high, high_words)])
+
+
+def _ef_padding_check(words: torch.Tensor, n: int, k: int) -> None:
+    """The bits of a blob that no code sets: at or past ``high_bits`` of the high section, past ``k b`` of the low."""
+    b, low_words, high_bits, high_words = ef_plan(n, k)
+    if high_bits % 32 and (int(words[-1]) & _U32) >> (high_bits % 32):
+        raise ValueError(f"Elias-Fano index: a bit is set at or past the {high_bits} bits of the high section")
+    if k * b % 32 and (int(words[low_words - 1]) & _U32) >> (k * b % 32):
+        raise ValueError("Elias-Fano index: the padding bits after the low fields are not zero")
+
+
+def ef_decoded_check(words: torch.Tensor, idx: torch.Tensor, count, n: int, k: int) -> None:
+    """What a decoder's output for one blob must satisfy before it is taken for a code (the device decoder writes
+    whatever the words spell and leaves the verdict to this check; :func:`ef_decode` runs it on its own result):
+    ``count``, the set bits of the high section, is ``k``; no padding bit is set; every decoded index is in ``[0, n)``
+    (the device writes -1 otherwise).  Ascending and distinct follow from the format.  Raises ``ValueError``."""
+    if int(count) != k:
+        raise ValueError(f"Elias-Fano index: the high section holds {int(count)} set bits, expected k = {k}")
+    _ef_padding_check(words, n, k)
+    bad = ((idx < 0) | (idx >= n)).nonzero()
+    if bad.numel():
+        raise ValueError(f"Elias-Fano index: the index decoded at rank {int(bad[0])} is outside [0, {n})")
+
+
+def ef_decode(words: torch.Tensor, n: int, k: int) -> torch.Tensor:
+    """One blob of :func:`ef_plan` -> ``idx`` int32 ``[k]``.  The set bit of rank ``i`` at position ``p`` of the high
+    section gives ``high = p - i``, field ``i`` of the low section ``low``, ``idx_i = (high << b) | low``.  Raises
+    ``ValueError`` for words that :func:`ef_encode` cannot have made: another popcount than ``k``, a set bit at or past
+    ``high_bits``, a non-zero padding bit, a decoded index ``>= n``."""
+    b, low_words, high_bits, high_words = ef_plan(n, k)
+    if words.dtype != torch.int32 or words.dim() != 1 or words.numel() != low_words + high_words:
+        raise ValueError(f"Elias-Fano index: expected an int32 [{low_words + high_words}] tensor (got {words.dtype} "
+                         f"{tuple(words.shape)})")
+    pos = _ef_bits(words[low_words:]).nonzero().flatten()
+    idx = torch.full((k,), -1, dtype=torch.int64, device=words.device)
+    if pos.numel() == k:
+        low = (_ef_bits(words[:low_words])[:k * b].view(k, b) << torch.arange(b, device=words.device)).sum(1)
+        idx = ((pos - torch.arange(k, device=words.device)) << b) | low
+    ef_decoded_check(words, idx, pos.numel(), n, k)
+    return idx.to(torch.int32)
+
+
+# ---------------------------------------------------------------------------------------
 # Low-rank (PowerSGD) uploads with error feedback (oracle of csrc/lowrank_delta.hip)
 # ---------------------------------------------------------------------------------------
 LOWRANK_RANKS = (1, 2, 4, 8)

@@ -3,6 +3,7 @@
 quantised codes of parallel/quantize.py (of the rotated delta: parallel/rotate.py), the sign bits of parallel/sign.py, the
 low-rank factors of parallel/lowrank.py or the count sketch of parallel/sketch.py -- one interface, so that the star drivers hold one path for all six.  ``bind(flat_params)``, once
 after the model is built, gives a codec the layout of the flat buffer (the low-rank and the sketch codec need it).
+With ``upload_index=ef`` the three forms that carry an index list are wrapped by parallel/index_code.py, which codes that list.
 
 ``compress(local, theta_g, residual, client, round)`` makes the payload (the flat model, ``(idx, val)``, an ``Upload``),
 ``finite`` tells whether a coordinator may take it, ``pack`` / ``unpack(blob, n)`` are its wire tensor (``unpack``
@@ -35,11 +36,13 @@ class StarUpload:
     def from_cfg(cfg, driver: str) -> "StarUpload":
         """The codec of ``cfg``; every option is rejected where it cannot hold (``driver``: the federation
         driver that asks).  Outside the star only the dense codec's ``rule`` means anything."""
-        from .lowrank import LowRank  # (StarUploads themselves: both modules import this one)
+        from .index_code import IndexCoded  # (StarUploads themselves: these modules import this one)
+        from .lowrank import LowRank
         from .quantize import Quantizer
         from .rotate import RotatedQuantizer
         from .sign import SignUpload
         from .sketch import SketchUpload
+        coded = IndexCoded.check_cfg(cfg, driver)
         rule = RobustRule.from_cfg(cfg, driver)
         sparse = Sparsifier.from_cfg(cfg, driver)
         quant = Quantizer.from_cfg(cfg, driver)
@@ -48,13 +51,15 @@ class StarUpload:
         sketch = SketchUpload.from_cfg(cfg, driver)
         sign = SignUpload.from_cfg(cfg, driver)
         if sign.active:
-            return sign
+            return IndexCoded(sign) if coded else sign
         if sketch.active:
             return sketch
         if low.active:
             return low
         if rot.active:
             return rot
+        if coded:  # (with upload_topk > 0: check_cfg)
+            return IndexCoded(quant if quant.active else TopkUpload(sparse))
         return quant if quant.active else TopkUpload(sparse) if sparse.active else DenseUpload(rule)
 
     def bind(self, flat_params) -> "StarUpload":
@@ -162,6 +167,10 @@ class TopkUpload(StarUpload):
 
     def unpack(self, blob, n):
         return Sparsifier.unpack(blob, n, self.sparse.k_for(n))
+
+    def words_for(self, n: int) -> int:
+        """int32 words of a packed upload."""
+        return 2 * self.sparse.k_for(n)
 
     def received(self, base, up):
         out = base.detach().clone()
